@@ -12,11 +12,17 @@ fp32, 128x128 RGB, batch 64 PER GPU (weak scaling), synthetic U[-1,1] images res
 random-init weights.  One "step" = one train_batch(): D phase incl. second-order R1 backward,
 D Adam, G phase, G Adam, EMA, and the reference's loss read-back (one host sync per step).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel family (the MFMA
+Rank 0 prints ONE JSON line.  `roofline_step` is the whole step against the fp32 MFMA floor
+(SURVEY.md §8d).  A plain run sets up, warms up, times the K steps and prints the line; what
+takes runs of its own comes with --full: `roofline` for the dominant kernel family (the MFMA
 implicit-GEMM convolution, fwd+dgrad), timed with HIP events on the launch stream in an
-instrumented eager pass of the same step right after the timed region; `roofline_step` is
-the whole step against the fp32 MFMA floor.  `cpu_baseline` is the CPU oracle
-(oracle/sagan_cpu.py, kind "port") timed on this host on a bounded sample.
+instrumented eager pass of the same step right after the timed region, `roofline_1x1`,
+`kernel_time_ms`, and `cpu_baseline`, the CPU oracle (oracle/sagan_cpu.py, kind "port") timed
+on this host on a bounded sample.
+
+--dump-outputs DIR writes what the last timed step produced, before anything else runs: the
+losses train_batch() returns (float64) and the updated state of g, target_g and d, each network's
+floating-point state_dict() entries flattened in order into one float32 array.
 """
 import argparse
 import json
@@ -44,8 +50,12 @@ def parse():
     p.add_argument('--trainer', default='cnn', choices=['cnn', 'iqn'])
     p.add_argument('--batch', type=int, default=64, help='per-GPU batch')
     p.add_argument('--eager', action='store_true', help='do not replay HIP graphs')
-    p.add_argument('--no-cpu-baseline', action='store_true')
-    p.add_argument('--no-kernel-timing', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also the instrumented kernel-timing pass (roofline, roofline_1x1, kernel_time_ms) and the CPU baseline')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the last timed step\'s losses and network state to DIR/<name>.npy')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
+    p.add_argument('--no-kernel-timing', action='store_true', help='with --full: leave out the kernel-timing pass')
     p.add_argument('--cpu-batch', type=int, default=None, help='batch of the CPU-baseline sample (default: --batch)')
     p.add_argument('--sync-bn', action='store_true', help='N>1: BatchNorm statistics of the GLOBAL batch (SyncBN)')
     p.add_argument('--overlap', choices=['off', 'on', 'auto', 'tune'], default='auto',
@@ -60,7 +70,10 @@ def parse():
                    help='N=1 only: a ONE-rank RCCL group with DataParallel(rehearse=True) -- every collective of an N-rank step is '
                         'issued (bucket all-reduces on the side stream, SyncBN sums inside the graphs) and is the identity; '
                         'measures what the collectives cost the step apart from the wire')
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error('--steps must be at least 1')
+    return a
 
 
 def make_trainer(config, kind, batch, device):
@@ -290,6 +303,30 @@ def cpu_baseline(config, kind, batch):
                        f'{batch}, oracle/sagan_cpu.py (plain PyTorch CPU fp32); host has {phys} physical cores / {logical} logical CPUs')
 
 
+DUMP_LIMIT_BYTES = 63_000_000       # array bytes; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(tr, logs, out_dir):
+    """--dump-outputs: the last timed step's losses and the networks' state after it, as DIR/<name>.npy.  Should the
+    networks' state exceed the 64 MB budget, each network is written as the same fixed, seeded sample of its entries."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in logs.items()}
+    nets = ('g', 'target_g', 'd')
+    for name in nets:
+        sd = getattr(tr, name).state_dict()
+        arrays[name] = torch.cat([v.detach().reshape(-1).float() for v in sd.values() if v.is_floating_point()]).cpu().numpy()
+    net_bytes = sum(arrays[n].nbytes for n in nets)
+    room = DUMP_LIMIT_BYTES - sum(v.nbytes for k, v in arrays.items() if k not in nets)
+    if net_bytes > room:
+        for name in nets:
+            v = arrays[name]
+            idx = np.random.default_rng(0).choice(v.size, v.size * room // net_bytes, replace=False)
+            arrays[name] = v[np.sort(idx)]
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), v)
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -396,9 +433,11 @@ def main():
         dt = float(t)
     ms_per_step = dt / a.steps * 1e3
     value = a.batch * world * a.steps / dt
+    if a.dump_outputs and rank == 0:            # before the --full pass below, whose steps move the weights on
+        dump_outputs(tr, logs, a.dump_outputs)
 
     agg = {}
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         # instrumented eager pass of the same step (same kernels, same shapes) with HIP events on the launch stream;
         # every rank runs it (the step's collectives must stay matched), rank 0 reports its own kernels
         saved = (getattr(tr, '_graphs', None), getattr(tr, '_graph_requested', False), tr.rng_feed.mode)
@@ -467,7 +506,7 @@ def main():
             ex = sum(d['flops'] for d in agg.values())
             out['roofline_step']['executed_flop_per_step'] = ex
             out['roofline_step']['executed_tflops'] = round(ex / (ms_per_step * 1e-3) / 1e12, 3)
-        if not a.no_cpu_baseline and world == 1:       # reported at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:       # reported at N = 1 only
             out['cpu_baseline'] = cpu_baseline(a.config, a.trainer, a.cpu_batch or a.batch)
         print(json.dumps(out), flush=True)
     if world > 1 or rehearse:

@@ -1,12 +1,11 @@
-"""INTEGRATION.md section 1, executed: tartangan's own ``Trainer`` (imported from the reference tree, build container
-only) subclassed exactly as the snippet shows, delegating ``build_models`` / ``train_batch`` to the HIP-engine trainer;
-run over the emulator and compared with the fixture the reference's own CNNTrainer produced.  Skipped where the
-reference tree is absent (it never travels to the GPU box)."""
+"""INTEGRATION.md section 1, executed: tartangan's ``Trainer`` subclassed exactly as the snippet shows, delegating
+``build_models`` / ``train_batch`` to the HIP-engine trainer; run over the emulator and compared with the fixture the
+reference's own CNNTrainer produced.  The base class is the reference's own ``Trainer`` where the reference tree is
+present, and elsewhere ``tartangan_amd.trainers.trainer.Trainer``, which keeps the reference base class's interface."""
 import argparse
 import os
 import sys
 
-import pytest
 import torch
 
 from conftest import REPO, load_golden
@@ -14,13 +13,21 @@ from emulator import Emulator
 from oracle.procedural import procedural_state, synthetic_images
 
 REFERENCE = os.environ.get('TARTANGAN_REFERENCE', '/root/reference')
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, 'tartangan')), reason='reference tree not present')
+
+
+def trainer_base():
+    """The reference's ``Trainer`` if its tree is readable here, else the project's own."""
+    if os.path.isdir(os.path.join(REFERENCE, 'tartangan')):
+        sys.path.insert(0, os.path.join(REPO, 'tests', 'golden'))
+        import make_golden      # noqa: F401  registers the inert torchvision / smart_open / boto3 stand-ins + sys.path
+        from tartangan.trainers.trainer import Trainer           # the REFERENCE's Trainer
+    else:
+        from tartangan_amd.trainers.trainer import Trainer
+    return Trainer
 
 
 def test_reference_trainer_subclass_delegating_to_the_hip_step(single_thread):
-    sys.path.insert(0, os.path.join(REPO, 'tests', 'golden'))
-    import make_golden          # noqa: F401  registers the inert torchvision / smart_open / boto3 stand-ins + sys.path
-    from tartangan.trainers.trainer import Trainer               # the REFERENCE's Trainer
+    Trainer = trainer_base()
     from tartangan_amd import backend
     from tartangan_amd.models.pluggan import GAN_CONFIGS
     from tartangan_amd.trainers.cnn import CNNTrainer as _HipStep

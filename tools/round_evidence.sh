@@ -30,7 +30,7 @@ PY
 rm -rf $out/gstats
 cd $root
 python3 tools/kernel_stats_summary.py $out/${tag}_kernel_stats_128a3_cnn_b64.csv 60 > $out/${tag}_kernel_stats_summary.txt
-python3 bench.py > $out/${tag}_bench_default.json 2> $out/bench_default.err
+python3 bench.py --full > $out/${tag}_bench_default.json 2> $out/bench_default.err
 python3 bench.py --gpus 2 --share-gpu --backend gloo --steps 3 --warmup 3 > $out/${tag}_bench_2rank_gloo.json 2> $out/bench_2rank.err || echo "2-rank rehearsal failed" >> $out/bench_2rank.err
 bash tools/bench_configs.sh > $out/${tag}_bench_configs.txt 2>&1
 head -c 600 $out/${tag}_bench_default.json; echo; head -c 400 $out/${tag}_bench_2rank_gloo.json; echo; head -3 $out/${tag}_kernel_stats_summary.txt; cat $out/${tag}_bench_configs.txt; head -8 $out/${tag}_gemm_big.txt
