@@ -3,7 +3,7 @@
 // deterministic (fp32 per-thread partials over <= ~64 elements, fp64 across threads/blocks).
 //
 // Notation per channel (n = B*HW): xhat = (x-mean)*invstd, y = gamma*xhat+beta,
-// s = lrelu'(y) in {1, slope}, gyh = gz*s.
+// s = lrelu'(y) in {1, slope} (1 only for y > 0: torch's derivative at y == 0 is slope), gyh = gz*s.
 //   fwd : z = y*s
 //   bwd : gbeta = S(gyh); ggamma = S(gyh*xhat); gx = gamma*invstd*(gyh - gbeta/n - xhat*ggamma/n)
 //   dbwd: see tg_bn_act_dbwd below (derivation in DESIGN.md "BatchNorm second backward").
@@ -193,7 +193,7 @@ struct RedBwd {
   }
   __device__ void elem(float g, float xv, float* acc) {
     const float y = bn_y(xv, a, b);
-    const float gyh = y >= 0.f ? g : g * slope;
+    const float gyh = y > 0.f ? g : g * slope;
     acc[0] += gyh;
     acc[1] += gyh * ((xv - mu) * r);
   }
@@ -236,7 +236,7 @@ struct BwdBody {
   int add_vc_end;            // ... for the virtual channels below this (the leading groups; `add` holds only their images)
   __device__ float elem(float g, float xv, float a, float b, float mu, float r, float k1, float k2) const {
     const float y = bn_y(xv, a, b);
-    const float gyh = y >= 0.f ? g : g * slope;
+    const float gyh = y > 0.f ? g : g * slope;
     return training ? a * (gyh - k1 - ((xv - mu) * r) * k2) : a * gyh;
   }
   __device__ void vec4(const Chan& ch, int64_t off) const {
@@ -292,7 +292,7 @@ struct BwdSumsBody {
   }
   __device__ float elem(float g, float xv) const {
     const float y = bn_y(xv, a, b);
-    const float gyh = y >= 0.f ? g : g * slope;
+    const float gyh = y > 0.f ? g : g * slope;
     return training ? a * (gyh - k1 - ((xv - mu) * r) * k2) : a * gyh;
   }
   struct V { float4 g, v, t; };
@@ -321,7 +321,7 @@ struct RedDbwd {
   }
   __device__ void elem(float vv, float g, float xv, float* acc) {
     const float y = bn_y(xv, a, b);
-    const float gyh = y >= 0.f ? g : g * slope;
+    const float gyh = y > 0.f ? g : g * slope;
     const float xh = (xv - mu) * r;
     acc[0] += vv; acc[1] += vv * xh; acc[2] += gyh; acc[3] += gyh * xh; acc[4] += vv * gyh;
   }
@@ -372,7 +372,7 @@ struct DbwdBody {
   }
   __device__ void elem(const Ch& h, float vv, float g, float xv, float& o_gz, float& o_x) const {
     const float y = bn_y(xv, h.a, h.b);
-    const float s = y >= 0.f ? 1.f : slope;
+    const float s = y > 0.f ? 1.f : slope;
     const float gyh = g * s;
     const float xh = (xv - h.mu) * h.r;
     const float pv = vv - h.k0 - xh * h.k1;
@@ -556,7 +556,7 @@ __global__ void __launch_bounds__(SB) bn_small_bwd_kernel(const float* __restric
     for (int i = 0; i < SPER; ++i) {
       const float xv = ix.ok[i] ? x[ix.off[i]] : mu;
       const float gg = ix.ok[i] ? gz[ix.off[i]] : 0.f;
-      gyh[i] = bn_y(xv, a, b) >= 0.f ? gg : gg * slope;
+      gyh[i] = bn_y(xv, a, b) > 0.f ? gg : gg * slope;
       xh[i] = (xv - mu) * r;
     }
     float a0 = 0.f, a1 = 0.f;
@@ -676,7 +676,7 @@ __global__ void __launch_bounds__(SB) bn_small_bwd2_kernel(const float* __restri
     const int64_t off = base + (ok ? small2_off(e, HW, C, c) : 0);
     const float xv = ok ? x[off] : mu;
     const float gg = ok ? gz[off] : 0.f;
-    gyh[i] = bn_y(xv, a, b) >= 0.f ? gg : gg * slope;
+    gyh[i] = bn_y(xv, a, b) > 0.f ? gg : gg * slope;
     xh[i] = (xv - mu) * r;
   }
   float a0 = 0.f, a1 = 0.f;
@@ -735,7 +735,7 @@ __global__ void __launch_bounds__(DSB) bn_small_dbwd_kernel(const float* __restr
     const float xv = ix.ok[i] ? x[ix.off[i]] : mu;
     vv[i] = ix.ok[i] ? v[ix.off[i]] : 0.f;
     const float g = ix.ok[i] ? gz[ix.off[i]] : 0.f;
-    sl[i] = bn_y(xv, gr, b) >= 0.f ? 1.f : slope;
+    sl[i] = bn_y(xv, gr, b) > 0.f ? 1.f : slope;
     gyh[i] = g * sl[i];
     xh[i] = (xv - mu) * r;
   }

@@ -14,7 +14,7 @@ struct OpAdd { __device__ float operator()(float a, float b) const { return a + 
 struct OpMul { __device__ float operator()(float a, float b) const { return a * b; } };
 struct OpLreluBwd {   // a = g, b = x
   float slope;
-  __device__ float operator()(float g, float x) const { return x >= 0.f ? g : g * slope; }
+  __device__ float operator()(float g, float x) const { return x > 0.f ? g : g * slope; }
 };
 struct OpTanhBwd {    // a = g, b = y
   __device__ float operator()(float g, float y) const { return g * (1.f - y * y); }

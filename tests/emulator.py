@@ -318,7 +318,7 @@ class Emulator:
         xv = _v(x, B, C, HW)
         xhat = (xv - mean.view(1, C, 1)) * invstd.view(1, C, 1)
         y = xhat * gamma.view(1, C, 1) + beta.view(1, C, 1)
-        s = torch.where(y >= 0, torch.ones_like(y), torch.full_like(y, slope))
+        s = torch.where(y > 0, torch.ones_like(y), torch.full_like(y, slope))
         return xhat, y, s
 
     def bn_act_fwd(self, x, mean, invstd, gamma, beta, slope, z, B, C, HW):
@@ -620,7 +620,7 @@ class Emulator:
         return 0
 
     def lrelu_bwd(self, g, x, slope, out, n):
-        out.copy_(torch.where(x >= 0, g, g * slope))
+        out.copy_(torch.where(x > 0, g, g * slope))
         return 0
 
     def elu_fwd(self, x, alpha, scale, y, n):
