@@ -1068,13 +1068,13 @@ int tg_bn_sync_bwd_finish(const float* gz, const float* x, const float* mean, co
   TG_CHECK_PTR(gz); TG_CHECK_PTR(x); TG_CHECK_PTR(mean); TG_CHECK_PTR(invstd); TG_CHECK_PTR(gamma); TG_CHECK_PTR(beta);
   TG_CHECK_PTR(local_sums); TG_CHECK_PTR(global_sums); TG_CHECK_PTR(ggamma); TG_CHECK_PTR(gbeta); TG_CHECK_PTR(workspace);
   TG_CHECK_POS(B); TG_CHECK_POS(C); TG_CHECK_POS(HW);
-  if (count_global <= 0) return TG_EINVAL;
+  if (count_global <= 0 || (gx_add != nullptr && gx == nullptr)) return TG_EINVAL;
   hipStream_t st = tg_stream(stream);
   Parts p = split_ws(workspace, B, C, HW);
   sync_bwd_finish<<<chan_grid(C), 64, 0, st>>>(local_sums, global_sums, (double)count_global, ggamma, gbeta, p.coef, C, accumulate);
   if (gx != nullptr) {
     BwdBody body{gz, x, gx, mean, invstd, gamma, beta, p.coef, slope, 1, gx_add, C};
-    planes::launch_map(body, B, C, HW, st, tg_aligned16(x) && tg_aligned16(gz) && tg_aligned16(gx));
+    planes::launch_map(body, B, C, HW, st, tg_aligned16(x) && tg_aligned16(gz) && tg_aligned16(gx) && (!gx_add || tg_aligned16(gx_add)));
   }
   return tg_launch_status();
 }

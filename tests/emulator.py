@@ -402,8 +402,11 @@ class Emulator:
         return 0
 
     def bn_sync_stats_finish(self, sums, world, mean, invstd, rm, rv, nbt, momentum, eps, count_global, replicate, C):
+        if (rm is None) != (rv is None):
+            return -1                            # TG_EINVAL, nothing touched
         if nbt is not None:
             nbt.add_(1)
+        eps = float(torch.tensor(eps, dtype=torch.float32))      # the C ABI takes eps as a float
         s = sums.view(C, 3) / world
         m = s[:, 0]
         var = (s[:, 2] + (s[:, 1] - m * m)).clamp_min(0)

@@ -125,8 +125,26 @@ def _oracle(fx):
     return ref
 
 
-def oracle_d_phase(fx, seed, dtype):
-    """oracle/sagan_cpu.py OracleTrainer.train_batch's D phase (up to d_loss.backward()) on the state cast to ``dtype``."""
+_ORACLE_RUNS = {}
+
+
+def oracle_d_phase(fx, seed, dtype, buffers=None):
+    """oracle/sagan_cpu.py OracleTrainer.train_batch's D phase (up to d_loss.backward()) on the state cast to ``dtype``:
+    the losses and every parameter gradient.  ``buffers``: a key prefix under which D's BatchNorm buffers after the phase (the
+    oracle updates them in place: the real pass, then the fake pass) are returned as well -- running statistics as float64,
+    num_batches_tracked as it is.  A (fixture, seed, dtype) is computed once per process."""
+    import json
+    key = (json.dumps(fx, sort_keys=True), seed, dtype)
+    if key not in _ORACLE_RUNS:
+        _ORACLE_RUNS[key] = _oracle_d_phase(fx, seed, dtype)
+    out, bufs = _ORACLE_RUNS[key]
+    out = dict(out)
+    if buffers is not None:
+        out.update({buffers + k: v for k, v in bufs.items()})
+    return out
+
+
+def _oracle_d_phase(fx, seed, dtype):
     from oracle import sagan_cpu as O
     ref = _oracle(fx)                                        # (sets the oracle's activation option for this case)
     S = {}
@@ -150,7 +168,9 @@ def oracle_d_phase(fx, seed, dtype):
     d_loss.backward()
     out = {'d_loss': d_loss.detach(), 'gp': gp.detach()}
     out.update({k: v.grad for k, v in S.items() if O.is_param(k) and v.grad is not None})
-    return {k: v.to(torch.float64) for k, v in out.items()}
+    bufs = {k: (v.to(torch.float64) if v.is_floating_point() else v.clone()) for k, v in S.items()
+            if 'running_' in k or 'num_batches_tracked' in k}
+    return {k: v.to(torch.float64) for k, v in out.items()}, bufs
 
 
 def hip_d_phase(fx, seed):
