@@ -439,6 +439,34 @@ int tg_trace(const float* A, float* out, int D, int ld, void* stream);
 /* rows[n] = sum_c p[n][c] * (log p[n][c] - log mean[c])  (the KL term of calculate_inception_score) */
 int tg_is_kl_rows(const float* p, const float* mean, float* rows, int N, int Cn, void* stream);
 
+/* ---------------------------------------------------------------- Inception-v3 forward (the network itself)
+ * What torchvision's Inception3 runs in eval mode between the preprocess above and the FID math: BasicConv2d =
+ * nn.Conv2d(bias=False) -> nn.BatchNorm2d(eps=0.001) -> F.relu, F.max_pool2d(3, stride=2), F.avg_pool2d(3, stride=1,
+ * padding=1) and torch.cat over channels.  Forward only.
+ *
+ * tg_inception_conv_fwd: y[:, y_coff : y_coff + Cout] = act(conv2d(x[:, x_coff : x_coff + Cin], w, stride, (ph, pw)) + bias)
+ * as an implicit GEMM on the fp32-input MFMA (M = Cout, N = B * OH * OW, K = Cin * KH * KW; exact fp32, no atomics,
+ * bit-identical from run to run).  x is (B, x_ctot, H, W), y is (B, y_ctot, OH, OW) with OH = (H + 2 ph - KH) / stride + 1
+ * (OW alike); channels outside the two slices are neither read nor written, so branches of a Mixed block write straight into
+ * its concatenated output and stacked 1x1 branches are read back by slices.  Any KH x KW (1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1,
+ * ...), stride 1 or 2, any zero padding per axis, any Cin / Cout.  bias (nullable, Cout floats) carries the folded BatchNorm;
+ * relu != 0 applies max(., 0).
+ * wp is the filter PACKED BY THE HOST, once per model: tg_inception_conv_weight_floats(Cin, Cout, KH, KW) floats, 16-byte
+ * aligned, wp[k][co] with row length CoutP = Cout rounded up to 128 and Kp = K rounded up to 16 rows, k = (ci * KH + kh) * KW
+ * + kw (the OIHW filter flattened and transposed), zero in the padding.                                               */
+size_t tg_inception_conv_weight_floats(int Cin, int Cout, int KH, int KW);
+int tg_inception_conv_supported(int B, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int ph, int pw,
+                                int x_ctot, int y_ctot);
+int tg_inception_conv_fwd(const float* x, const float* wp, const float* bias /*nullable*/, float* y, int B, int Cin, int Cout,
+                          int H, int W, int KH, int KW, int stride, int ph, int pw, int relu, int x_ctot, int x_coff,
+                          int y_ctot, int y_coff, void* stream);
+/* F.max_pool2d(x, 3, stride=2) (no padding: OH = (H - 3) / 2 + 1) and F.avg_pool2d(x, 3, stride=1, padding=1) (divides by 9
+ * everywhere, count_include_pad=True) of channels [x_coff, x_coff + C) into channels [y_coff, y_coff + C). */
+int tg_inception_maxpool3s2(const float* x, float* y, int B, int C, int H, int W, int x_ctot, int x_coff, int y_ctot,
+                            int y_coff, void* stream);
+int tg_inception_avgpool3(const float* x, float* y, int B, int C, int H, int W, int x_ctot, int x_coff, int y_ctot,
+                          int y_coff, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline
  * ImageBytesDataset (image_bytes_dataset.py:12-49) + ToPILImage -> RandomCrop(size) -> ToTensor -> Normalize(.5, .5)
  * (trainers/trainer.py:69-78) for a whole batch: archive = device-resident uint8 (n_images, H, W, channels) exactly

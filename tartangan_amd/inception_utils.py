@@ -9,20 +9,24 @@ including its in-place centring of the argument), ``sqrt_newton_schulz`` (:129-1
 ``torch_calculate_frechet_distance`` (:205-235), ``calculate_inception_score`` (:239-246),
 ``prepare_inception_metrics`` / ``get_inception_metrics`` (:285-328) and, for a data-parallel run, the rank-sharded
 form of the moments (``sharded_moments``: all-reduce of the column sums, then of the centred X^T X).
-The Inception-v3 network itself is the caller's: its pretrained weights come from the network (``inception_v3(
-pretrained=True)``, :273) and cannot be fetched offline -- ``WrapInception`` takes any module with
+The Inception-v3 forward itself is ``models.inception.Inception3`` (fp32 MFMA implicit-GEMM convolutions with the BatchNorm
+folded in, csrc/inception.hip); only its pretrained weights are external: the reference downloads them (``inception_v3(
+pretrained=True)``, :273), which cannot be done offline, so ``load_inception_net(weights=...)`` /
+``TG_INCEPTION_WEIGHTS`` name a torchvision-format state dict on disk.  ``WrapInception`` still takes any module with
 torchvision's Inception3 attribute names, ``prepare_inception_metrics`` any ``net`` returning ``(pool, logits)``.
 
 The products run on ``tg_gemm_big`` (fp32 MFMA, 128 x 128 tiles, LDS-DMA): one Newton-Schulz
 evaluation at 2048 features is 61 products of 2048^3 = 1.05 TFLOP.  No CPU fallback: device tensors only.
 """
 import math
+import os
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import backend as _be
+from .models.inception import Inception3
 
 VGG_MEAN = torch.tensor([0.485, 0.456, 0.406])[..., None, None]       # inception_utils.py:29-30
 VGG_STD = torch.tensor([0.229, 0.224, 0.225])[..., None, None]
@@ -191,6 +195,9 @@ class WrapInception(nn.Module):
         self.std = nn.Parameter(torch.tensor([0.229, 0.224, 0.225]).view(1, -1, 1, 1), requires_grad=False)
 
     def _features(self, x):
+        if isinstance(self.net, Inception3):            # the native network: one stream of launches, (pool, logits) directly
+            pool, logits = self.net(x)
+            return pool.clone(), logits.clone()         # (its outputs are cached buffers; callers keep these across calls)
         for name in self.LAYERS:
             x = nn.functional.max_pool2d(x, kernel_size=3, stride=2) if name == 'pool' else getattr(self.net, name)(x)
         pool = torch.mean(x.view(x.size(0), x.size(1), -1), 2)
@@ -230,9 +237,19 @@ def accumulate_inception_activations(sample, net, num_inception_images=50000):
     return torch.cat(pool, 0), torch.cat(probs, 0)
 
 
-def load_inception_net(parallel=False, net=None):
+def load_inception_net(parallel=False, net=None, weights=None):
     """inception_utils.py:271-278.  The pretrained Inception-v3 weights come from the network; offline the caller supplies
-    the loaded torchvision model (``net``)."""
+    the loaded torchvision model (``net``) or names the weights: ``weights`` (or the environment variable
+    ``TG_INCEPTION_WEIGHTS``) is the path of a torchvision-format state dict, e.g. the published
+    ``inception_v3_google-*.pth``, loaded into the native ``Inception3``."""
+    if net is None:
+        weights = weights if weights is not None else (os.environ.get('TG_INCEPTION_WEIGHTS') or None)
+    if net is None and weights is not None:
+        state = torch.load(weights, map_location='cpu')
+        if not isinstance(state, dict) or 'fc.weight' not in state:
+            raise RuntimeError(f'load_inception_net: {weights} is not an Inception-v3 state dict (no fc.weight)')
+        net = Inception3(num_classes=state['fc.weight'].shape[0])
+        net.load_state_dict(state)
     if net is None:
         try:
             from torchvision.models.inception import inception_v3
@@ -267,16 +284,16 @@ def sharded_moments(pool, group=None):
     return mu, xtx
 
 
-def prepare_inception_metrics(moments_path, device, parallel=False, no_fid=False, net=None, group=None):
+def prepare_inception_metrics(moments_path, device, parallel=False, no_fid=False, net=None, group=None, weights=None):
     """inception_utils.py:285-328 -> ``get_inception_metrics(sample, num_inception_images, num_splits=10, prints=True,
     use_torch=True)`` returning ``(IS_mean, IS_std, FID)``.  ``moments_path``: the .npz with ``mu`` / ``sigma`` written by
-    calculate_inception_moments.  ``net``: a loaded network, see ``load_inception_net``.  Under data parallelism
+    calculate_inception_moments.  ``net``: a loaded network, ``weights``: the path of a state dict for the native one, see ``load_inception_net``.  Under data parallelism
     (``group`` / an initialised default group) every rank samples its own share and the moments are combined with
     ``sharded_moments``; the per-sample class probabilities are gathered for the Inception score."""
     data = np.load(moments_path)
     data_mu = torch.tensor(data['mu']).float().to(device)
     data_sigma = torch.tensor(data['sigma']).float().to(device)
-    net = net if (net is not None and not isinstance(net, type)) else load_inception_net(parallel)
+    net = net if (net is not None and not isinstance(net, type)) else load_inception_net(parallel, weights=weights)
     if isinstance(net, nn.Module):
         net = net.to(device)
 

@@ -5,8 +5,9 @@ Same flags (``--inception-moments``, ``--n-inception-imgs``, ``--fid-freq``, ``-
 protocol and the same call: every ``fid_freq`` batches ``get_inception_metrics(trainer.sample_g, n_inception_imgs,
 num_splits=5)`` and the three values appended to ``logs``.  The Inception network is handed in (``net=`` or
 ``trainer.args.inception_net``: a loaded torchvision Inception3, a ``WrapInception``, or any module returning ``(pool,
-logits)``) because its pretrained weights have to come from the network; without one, ``on_train_begin`` raises with
-that explanation.  Under data parallelism every rank samples a share and the moments are reduced over the ranks
+logits)``), or ``--inception-weights`` (or ``TG_INCEPTION_WEIGHTS``) names a torchvision-format state dict for the native
+``models.inception.Inception3``; its pretrained weights have to come from the network, so with neither ``on_train_begin``
+raises with that explanation.  Under data parallelism every rank samples a share and the moments are reduced over the ranks
 (``inception_utils.sharded_moments``)."""
 import os
 import shutil
@@ -32,7 +33,8 @@ class FIDComponent(TrainerComponent):
             net = inception_utils.WrapInception(net.eval())             # a bare torchvision Inception3
         dp = getattr(self.trainer, 'data_parallel', None)
         self.get_inception_metrics = inception_utils.prepare_inception_metrics(
-            args.inception_moments, self.trainer.device, False, net=net, group=None if dp is None else dp.group)
+            args.inception_moments, self.trainer.device, False, net=net, group=None if dp is None else dp.group,
+            weights=getattr(args, 'inception_weights', None))
 
     def on_train_end(self, steps, logs):
         if self.model_path is not None:
@@ -56,6 +58,8 @@ class FIDComponent(TrainerComponent):
     def add_args_to_parser(cls, parser):
         parser.add_argument('--inception-moments', type=lambda v: None if v in (None, 'None', 'none') else str(v), default=None,
                             help='Path to pre-calculated inception moments')
+        parser.add_argument('--inception-weights', type=lambda v: None if v in (None, 'None', 'none') else str(v), default=None,
+                            help='Path to a torchvision-format Inception-v3 state dict (inception_v3_google-*.pth)')
         parser.add_argument('--n-inception-imgs', default=1000, type=int)
         parser.add_argument('--cleanup-inception-model', action='store_true')
         parser.add_argument('--fid-freq', default=10000, type=int, help='Calculate test metrics every N batches')
