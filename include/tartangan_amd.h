@@ -110,7 +110,8 @@ int tg_conv2d_wgrad(const float* x, const float* gy, float* gw, float* gbias /*n
  * as ONE pass each way: x is read once for the three outputs, the three output gradients give the input gradient in one pass
  * (no three-way add) and the three filter gradients in one pass.  w / gw: the three filters back to back,
  * [c0 + c1 + c2][Cin] (they are adjacent in the parameter bucket); y_k / gy_k: (B, c_k, H, W) each.  Bandwidth-bound
- * streaming kernels (no LDS); need H*W % 16 == 0, at most 64 channels either side, 16-byte aligned tensors. */
+ * streaming kernels (no LDS); need H*W % 16 == 0, at most 64 channels either side and EVERY pointer (filters and workspace included)
+ * 16-byte aligned: TG_EUNSUPPORTED otherwise, nothing written. */
 int tg_conv1x1_multi_supported(int c0, int c1, int c2, int B, int Cin, int H, int W);
 int tg_conv1x1_multi_fwd(const float* x, const float* w, float* y0, float* y1, float* y2, int c0, int c1, int c2,
                          int B, int Cin, int H, int W, void* stream);
@@ -473,7 +474,8 @@ int tg_inception_avgpool3(const float* x, float* y, int B, int C, int H, int W, 
  * as np.savez_compressed stores it, index[b] = image of batch row b (device int64), crop_y / crop_x = top-left corner
  * of the size x size crop per row (device int32, nullable = 0: image size == crop size, where RandomCrop draws nothing).
  * out (B, channels, size, size) fp32 = ((u8 / 255) - 0.5) / 0.5 in ToTensor's / Normalize's operation order.
- * The caller guarantees 0 <= index < n_images and crop + size <= H, W.                                            */
+ * The caller guarantees 0 <= index < n_images and crop + size <= H, W.  out must be 16-byte aligned (TG_EUNSUPPORTED
+ * otherwise); archive, index and the crops may sit at any multiple of their element size.                         */
 int tg_image_bytes_batch(const uint8_t* archive, const int64_t* index, const int* crop_y /*nullable*/,
                          const int* crop_x /*nullable*/, float* out, int B, int64_t n_images, int H, int W,
                          int channels, int size, void* stream);

@@ -3484,13 +3484,24 @@ int tg_poolconv3x3_fwd(const float* x, const float* w4, const float* bias, const
 int tg_poolconv3x3_dgrad(const float* gy, const float* wp, float* gx, int B, int Cin, int Cout, int H, int W, void* stream) {
   TG_CHECK_PTR(gy); TG_CHECK_PTR(wp); TG_CHECK_PTR(gx);
   if (!tg_poolconv3x3_supported(B, Cin, Cout, H, W)) return TG_EUNSUPPORTED;
-  if (((uintptr_t)gx & 7) != 0) return TG_EUNSUPPORTED;
+  hipStream_t st = tg_stream(stream);
   // the four-phase kernel with gy (Cout channels, H x W) as its low-resolution input and Cin output channels
-  Shape s{B, Cout, Cin, H, W};
-  const GeoId g = pick_geo(H, W);
-  const int vx = plane_vec_ok(gy, W), vw = tg_aligned16(wp);
-  launch_upfwd(g, gy, wp, nullptr, nullptr, gx, s, vx, vw, tg_stream(stream));
-  return tg_launch_status();
+  if (((uintptr_t)gx & 7) == 0) {
+    Shape s{B, Cout, Cin, H, W};
+    const GeoId g = pick_geo(H, W);
+    const int vx = plane_vec_ok(gy, W), vw = tg_aligned16(wp);
+    launch_upfwd(g, gy, wp, nullptr, nullptr, gx, s, vx, vw, st);
+    return tg_launch_status();
+  }
+  // gx off an 8-byte boundary (the kernel above stores float2 pairs): one launch per phase, as tg_upconv3x3_fwd does for such a y
+  for (int ph = 0; ph < 4; ++ph) {
+    Shape s{B, Cout, Cin, H, W};
+    s.oy = s.py = ph >> 1;
+    s.ox = s.px = ph & 1;
+    s.os = 2;
+    if (int rc = launch_fwd<2, false>(gy, wp + (size_t)ph * Cin * Cout * 4, nullptr, nullptr, gx, s, st)) return rc;
+  }
+  return TG_OK;
 }
 
 int tg_conv2d_dgrad(const float* gy, const float* w, float* gx, int B, int Cin, int Cout, int H, int W, int ks, void* stream) {
@@ -3553,7 +3564,7 @@ int tg_conv1x1_multi_fwd(const float* x, const float* w, float* y0, float* y1, f
                          int H, int W, void* stream) {
   TG_CHECK_PTR(x); TG_CHECK_PTR(w); TG_CHECK_PTR(y0); TG_CHECK_PTR(y1); TG_CHECK_PTR(y2);
   if (!qkv_ok(c0, c1, c2, B, Cin, H, W)) return TG_EUNSUPPORTED;
-  if (!tg_aligned16(x) || !tg_aligned16(y0) || !tg_aligned16(y1) || !tg_aligned16(y2)) return TG_EUNSUPPORTED;
+  if (!tg_aligned16(x) || !tg_aligned16(w) || !tg_aligned16(y0) || !tg_aligned16(y1) || !tg_aligned16(y2)) return TG_EUNSUPPORTED;
   Shape s{B, Cin, c0 + c1 + c2, H, W};
   return launch_conv1x1_segs(one_seg(x, Cin), w, nullptr, nullptr, three_segs(y0, y1, y2, c0, c1, c2), s, false, tg_stream(stream));
 }
@@ -3562,7 +3573,7 @@ int tg_conv1x1_multi_dgrad(const float* gy0, const float* gy1, const float* gy2,
                            int B, int Cin, int H, int W, void* stream) {
   TG_CHECK_PTR(gy0); TG_CHECK_PTR(gy1); TG_CHECK_PTR(gy2); TG_CHECK_PTR(w); TG_CHECK_PTR(gx);
   if (!qkv_ok(c0, c1, c2, B, Cin, H, W)) return TG_EUNSUPPORTED;
-  if (!tg_aligned16(gx) || !tg_aligned16(gy0) || !tg_aligned16(gy1) || !tg_aligned16(gy2)) return TG_EUNSUPPORTED;
+  if (!tg_aligned16(gx) || !tg_aligned16(w) || !tg_aligned16(gy0) || !tg_aligned16(gy1) || !tg_aligned16(gy2)) return TG_EUNSUPPORTED;
   // as an operation: c0 + c1 + c2 input channels (the three gradients), Cin output channels, the forward filter read transposed
   Shape s{B, c0 + c1 + c2, Cin, H, W};
   return launch_conv1x1_segs(three_segs(gy0, gy1, gy2, c0, c1, c2), w, nullptr, nullptr, one_seg(gx, Cin), s, true, tg_stream(stream));
@@ -3576,7 +3587,8 @@ int tg_conv1x1_multi_wgrad(const float* x, const float* gy0, const float* gy1, c
                            size_t workspace_bytes, int c0, int c1, int c2, int B, int Cin, int H, int W, int accumulate, void* stream) {
   TG_CHECK_PTR(x); TG_CHECK_PTR(gy0); TG_CHECK_PTR(gy1); TG_CHECK_PTR(gy2); TG_CHECK_PTR(gw); TG_CHECK_PTR(workspace);
   if (!qkv_ok(c0, c1, c2, B, Cin, H, W)) return TG_EUNSUPPORTED;
-  if (!tg_aligned16(x) || !tg_aligned16(gy0) || !tg_aligned16(gy1) || !tg_aligned16(gy2)) return TG_EUNSUPPORTED;
+  if (!tg_aligned16(x) || !tg_aligned16(gy0) || !tg_aligned16(gy1) || !tg_aligned16(gy2) || !tg_aligned16(gw) || !tg_aligned16(workspace))
+    return TG_EUNSUPPORTED;
   const int C = c0 + c1 + c2;
   if (workspace_bytes < tg_conv2d_wgrad_workspace(B, Cin, C, H, W, 1)) return TG_EWORKSPACE;
   const WgPlan p = wgrad_plan(B, Cin, C, H, W, 1);

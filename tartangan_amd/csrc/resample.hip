@@ -265,6 +265,8 @@ __global__ void __launch_bounds__(RS_BLOCK) maxpool2_fwd_kernel(const float* __r
   }
 }
 
+// VEC2: gx is 8-byte aligned (W is even), so each window row is one float2 store; otherwise four scalar stores
+template <bool VEC2>
 __global__ void __launch_bounds__(RS_BLOCK) maxpool2_bwd_kernel(const float* __restrict__ gy, const uint8_t* __restrict__ idx,
                                                                 float* __restrict__ gx, int64_t nout, int H, int W) {
   const int OW = W / 2, OH = H / 2;
@@ -276,8 +278,13 @@ __global__ void __launch_bounds__(RS_BLOCK) maxpool2_bwd_kernel(const float* __r
     float* d = gx + (bc * H + 2 * oh) * W + 2 * ow;
     const float g = gy[i];
     const int k = idx[i];
-    *reinterpret_cast<float2*>(d) = make_float2(k == 0 ? g : 0.f, k == 1 ? g : 0.f);
-    *reinterpret_cast<float2*>(d + W) = make_float2(k == 2 ? g : 0.f, k == 3 ? g : 0.f);
+    if (VEC2) {
+      *reinterpret_cast<float2*>(d) = make_float2(k == 0 ? g : 0.f, k == 1 ? g : 0.f);
+      *reinterpret_cast<float2*>(d + W) = make_float2(k == 2 ? g : 0.f, k == 3 ? g : 0.f);
+    } else {
+      d[0] = k == 0 ? g : 0.f; d[1] = k == 1 ? g : 0.f;
+      d[W] = k == 2 ? g : 0.f; d[W + 1] = k == 3 ? g : 0.f;
+    }
   }
 }
 
@@ -410,9 +417,12 @@ int tg_maxpool2_fwd(const float* x, float* y, uint8_t* idx, int BC, int H, int W
 
 int tg_maxpool2_bwd(const float* gy, const uint8_t* idx, float* gx, int BC, int H, int W, void* stream) {
   TG_CHECK_PTR(gy); TG_CHECK_PTR(idx); TG_CHECK_PTR(gx); TG_CHECK_POS(BC);
-  if (H < 2 || W < 2 || (H & 1) || (W & 1) || ((uintptr_t)gx & 7)) return TG_EUNSUPPORTED;
+  if (H < 2 || W < 2 || (H & 1) || (W & 1)) return TG_EUNSUPPORTED;
   const int64_t nout = (int64_t)BC * (H / 2) * (W / 2);
-  maxpool2_bwd_kernel<<<tg_ew_grid(nout, RS_BLOCK), RS_BLOCK, 0, tg_stream(stream)>>>(gy, idx, gx, nout, H, W);
+  if (((uintptr_t)gx & 7) == 0)
+    maxpool2_bwd_kernel<true><<<tg_ew_grid(nout, RS_BLOCK), RS_BLOCK, 0, tg_stream(stream)>>>(gy, idx, gx, nout, H, W);
+  else
+    maxpool2_bwd_kernel<false><<<tg_ew_grid(nout, RS_BLOCK), RS_BLOCK, 0, tg_stream(stream)>>>(gy, idx, gx, nout, H, W);
   return tg_launch_status();
 }
 

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from emulator import Emulator
+from guarded import rnd, run_both, workspace
 
 pytestmark = pytest.mark.gpu
 
@@ -16,36 +17,6 @@ def K():
 
 
 E = Emulator()
-
-
-def workspace(nbytes):
-    t = torch.zeros(int(nbytes) // 4 + 4)
-    t._is_ws = True
-    return t
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed + 1000 * len(shape) + sum(shape))
-    return torch.randn(*shape, generator=g) * scale
-
-
-def run_both(K, name, args, outs, tol=1e-5, atol=None, scratch=()):
-    """args: list of python scalars / CPU tensors / None; outs: indices of output tensors."""
-    scratch = list(scratch) + [i for i, a in enumerate(args) if torch.is_tensor(a) and getattr(a, '_is_ws', False)]
-    cpu = [a.clone() if torch.is_tensor(a) else a for a in args]
-    dev = [a.cuda() if torch.is_tensor(a) else a for a in args]
-    getattr(E, name)(*cpu)
-    getattr(K, name)(*dev)
-    torch.cuda.synchronize()
-    for i in outs:
-        want, got = cpu[i].float(), dev[i].cpu().float()
-        scale = float(want.abs().max()) if want.numel() else 1.0
-        err = float((want - got).abs().max()) if want.numel() else 0.0
-        lim = (atol if atol is not None else tol * max(scale, 1e-6))
-        assert err <= lim, f'{name} arg{i}: max err {err:.3e} > {lim:.3e} (scale {scale:.3e})'
-    for i, a in enumerate(args):      # inputs must not be modified
-        if torch.is_tensor(a) and i not in outs and i not in scratch:
-            assert torch.equal(dev[i].cpu(), a), f'{name} modified input {i}'
 
 
 CONV_SHAPES = [
@@ -92,7 +63,7 @@ def poison_lds(K):
     y = torch.empty(64, 32, 64, 64, device='cuda')
     K.conv2d_fwd(nan, w, None, None, y, 64, 32, 32, 64, 64, 3)
     gw = torch.empty_like(w)
-    ws = torch.empty(K.conv2d_wgrad_workspace(64, 32, 32, 64, 64, 3) // 4 + 4, device='cuda')
+    ws = torch.empty((K.conv2d_wgrad_workspace(64, 32, 32, 64, 64, 3) + 3) // 4, device='cuda')
     K.conv2d_wgrad(nan, nan, gw, None, ws, ws.numel() * 4, 64, 32, 32, 64, 64, 3, 0)
     nan8 = torch.full((64, 128, 8, 8), float('nan'), device='cuda')
     w8 = torch.full((128, 128, 3, 3), float('nan'), device='cuda')
@@ -112,7 +83,7 @@ def test_conv_step_shapes_full_batch_after_lds_poison(K, shape):
     run_both(K, 'conv2d_fwd', [x, w, b, None, torch.zeros(B, Cout, H, W), B, Cin, Cout, H, W, ks], [4], tol=2e-5)
     poison_lds(K)
     run_both(K, 'conv2d_dgrad', [gy, w, torch.zeros(B, Cin, H, W), B, Cin, Cout, H, W, ks], [2], tol=2e-5)
-    ws = torch.zeros(K.conv2d_wgrad_workspace(B, Cin, Cout, H, W, ks) // 4 + 4)
+    ws = workspace(K.conv2d_wgrad_workspace(B, Cin, Cout, H, W, ks))
     poison_lds(K)
     run_both(K, 'conv2d_wgrad', [x, gy, torch.zeros(Cout, Cin, ks, ks), torch.zeros(Cout), ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, 0],
              [2, 3], tol=5e-5, scratch=[4])
@@ -277,7 +248,7 @@ def test_stride2_weight_gradients_in_two_steps_are_bit_identical(K, shape):
     w0, b0 = rnd(Cout, Cin, 3, 3, seed=9).cuda(), rnd(Cout, seed=10).cuda()
     want = []
     for name, lo, hi in (('poolconv3x3', x, gy), ('upconv3x3', a, gyh)):
-        ws = torch.zeros(getattr(K, name + '_wgrad_workspace')(B, Cin, Cout, H, W) // 4 + 4, device='cuda')
+        ws = workspace(getattr(K, name + '_wgrad_workspace')(B, Cin, Cout, H, W)).cuda()
         gw, gb = w0.clone(), b0.clone()
         getattr(K, name + '_wgrad')(lo, hi, gw, ws, ws.numel() * 4, B, Cin, Cout, H, W, 1, gb)
         gw2 = w0.clone()
@@ -286,7 +257,7 @@ def test_stride2_weight_gradients_in_two_steps_are_bit_identical(K, shape):
     rows, got, keep = [], [], []
     for mode, (name, lo, hi) in enumerate((('poolconv3x3', x, gy), ('upconv3x3', a, gyh))):
         for with_bias, acc in ((1, 1), (0, 0)):
-            ws = torch.zeros(getattr(K, name + '_wgrad_workspace')(B, Cin, Cout, H, W) // 4 + 4, device='cuda')
+            ws = workspace(getattr(K, name + '_wgrad_workspace')(B, Cin, Cout, H, W)).cuda()
             getattr(K, name + '_wgrad_partials')(lo, hi, ws, ws.numel() * 4, B, Cin, Cout, H, W, with_bias)
             gw, gb = w0.clone(), b0.clone()
             rows.append([ws.data_ptr(), gw.data_ptr(), gb.data_ptr() if with_bias else 0, B, Cin, Cout, H, W, mode, acc])
@@ -354,7 +325,7 @@ def test_conv_wgrad(K, shape):
     x, gy = rnd(B, Cin, H, W), rnd(B, Cout, H, W, seed=3)
     nbytes = K.conv2d_wgrad_workspace(B, Cin, Cout, H, W, ks)
     assert nbytes > 0
-    ws = torch.zeros(nbytes // 4 + 4)
+    ws = workspace(nbytes)
     run_both(K, 'conv2d_wgrad', [x, gy, torch.zeros(Cout, Cin, ks, ks), None, ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, 0],
              [2], tol=5e-5, scratch=[4])
     # fused bias gradient + accumulate-into-existing (the flat .grad bucket path)
@@ -386,12 +357,12 @@ def test_conv_wgrad_batched_reduce_is_bit_identical(K):
         bias = i % 2 == 0
         gw0, gb0 = rnd(Cout, Cin, ks, ks, seed=200 + i).cuda(), rnd(Cout, seed=300 + i).cuda()
         nbytes = K.conv2d_wgrad_workspace(B, Cin, Cout, H, W, ks)
-        ws = torch.zeros(nbytes // 4 + 4).cuda()
+        ws = workspace(nbytes).cuda()
         a, ab = gw0.clone(), gb0.clone()
         K.conv2d_wgrad(x, gy, a, ab if bias else None, ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, 1)
         want.append((a, ab))
         b, bb = gw0.clone(), gb0.clone()
-        ws2 = torch.zeros(nbytes // 4 + 4).cuda()
+        ws2 = workspace(nbytes).cuda()
         K.conv2d_wgrad_partials(x, gy, ws2, ws2.numel() * 4, B, Cin, Cout, H, W, ks, int(bias))
         items.append([ws2.data_ptr(), b.data_ptr(), bb.data_ptr() if bias else 0, B, Cin, Cout, H, W, ks, 1])
         got.append((b, bb))
