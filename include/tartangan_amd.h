@@ -468,6 +468,27 @@ int tg_inception_maxpool3s2(const float* x, float* y, int B, int C, int H, int W
 int tg_inception_avgpool3(const float* x, float* y, int B, int C, int H, int W, int x_ctot, int x_coff, int y_ctot,
                           int y_coff, void* stream);
 
+/* ---------------------------------------------------------------- scene structure stage (since version 101)
+ * SceneStructureBlock.forward (models/blocks/scene.py:127-155): per patch p, F.affine_grid(theta[:, p], (B, 1, S, S),
+ * align_corners=False) and F.grid_sample(m[:, p], grid, 'bilinear', 'zeros', align_corners=False), stacked to (B, P, S, S);
+ * the sigmoid, the `1 -`, the noise multiply, the loop over the patches and the stack / permute are all inside one launch.
+ *   theta        (B, P*6)            what the patch_transforms Linear writes: [b][p][row 0..1][col 0..2]
+ *   mask_logits  (B, P*patch*patch)  raw output of the masks Linear; NULL = an opaque patch of ones (the full_masks branch)
+ *   noise        (patch, patch)      shared by every b and p; NULL = no noise
+ *   out          (B, P, S, S)        written completely
+ * Texel m[b,p,v,u] = (mask_logits ? 1 - sigmoid(l) : 1) * (noise ? noise[v,u] : 1); base grid x_j = (2j+1)/S - 1, y_i alike;
+ * gx = t00 x + t01 y + t02, gy = t10 x + t11 y + t12; sample at ix = ((gx+1) patch - 1)/2, iy alike; the four bilinear corners
+ * contribute zero where they fall outside the patch.
+ * tg_scene_patches_bwd: gtheta (B, P*6) and gmask_logits (B, P*patch*patch; NULL exactly when mask_logits is NULL) are written
+ * completely (zeros for texels no sample touches); noise gets no gradient.  Every sum has a fixed order (no atomics): two runs
+ * on the same inputs are bit-identical.
+ * 1 <= patch <= 16 (TG_EUNSUPPORTED above), any S, B, P >= 1, pointers at any multiple of 4 bytes; no workspace.          */
+int tg_scene_patches_fwd(const float* theta, const float* mask_logits /*nullable*/, const float* noise /*nullable*/, float* out,
+                         int B, int P, int patch, int S, void* stream);
+int tg_scene_patches_bwd(const float* gout, const float* theta, const float* mask_logits /*nullable*/,
+                         const float* noise /*nullable*/, float* gtheta, float* gmask_logits /*nullable*/,
+                         int B, int P, int patch, int S, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline
  * ImageBytesDataset (image_bytes_dataset.py:12-49) + ToPILImage -> RandomCrop(size) -> ToTensor -> Normalize(.5, .5)
  * (trainers/trainer.py:69-78) for a whole batch: archive = device-resident uint8 (n_images, H, W, channels) exactly

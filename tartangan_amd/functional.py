@@ -2408,6 +2408,63 @@ def attention_core(theta, phi, g):
 PAIR_SPECS[_AttnCore] = ('bbb', 'hhhhh', 'b')
 
 
+# =========================================================================== scene structure stage
+class _ScenePatchesBwd(Function):
+    """Gradients of ``_ScenePatches`` (one launch); first order only."""
+
+    @staticmethod
+    def forward(ctx, gout, theta, mask_logits, noise, patch, S):
+        B, P = theta.shape[0], theta.shape[1] // 6
+        gtheta = torch.empty_like(theta)
+        gmask = torch.empty_like(mask_logits) if mask_logits is not None else None
+        K().scene_patches_bwd(gout.contiguous(), theta, mask_logits, noise, gtheta, gmask, B, P, patch, S)
+        if gmask is None:
+            return gtheta
+        return gtheta, gmask
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        raise NotImplementedError('second-order derivative of scene_patches (the stage sits in the generator only)')
+
+
+class _ScenePatches(Function):
+    @staticmethod
+    def forward(ctx, theta, mask_logits, noise, patch, S):
+        theta = theta.contiguous()
+        mask_logits = mask_logits.contiguous() if mask_logits is not None else None
+        noise = noise.contiguous() if noise is not None else None
+        B, P = theta.shape[0], theta.shape[1] // 6
+        out = theta.new_empty(B, P, S, S)
+        K().scene_patches_fwd(theta, mask_logits, noise, out, B, P, patch, S)
+        ctx.save_for_backward(theta, mask_logits, noise)
+        ctx.geom = (patch, S)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        theta, mask_logits, noise = ctx.saved_tensors
+        grads = _ScenePatchesBwd.apply(gout, theta, mask_logits, noise, *ctx.geom)
+        if mask_logits is None:
+            return grads, None, None, None, None
+        return grads[0], grads[1], None, None, None
+
+
+def scene_patches(theta, mask_logits, noise, patch, S):
+    """The scene structure stage (reference models/blocks/scene.py:127-155) as one launch: ``theta`` (B, P*6) affine
+    transforms, ``mask_logits`` (B, P*patch*patch) or None (opaque patches), ``noise`` (patch, patch) or None -> (B, P, S, S):
+    patch p = (1 - sigmoid(logits)) * noise placed by ``F.affine_grid`` / ``F.grid_sample`` (bilinear, zeros,
+    align_corners=False).  Once differentiable; ``noise`` gets no gradient."""
+    if theta.dim() != 2 or theta.shape[1] % 6:
+        raise ValueError(f'scene_patches: theta must be (B, P*6), got {tuple(theta.shape)}')
+    P = theta.shape[1] // 6
+    if mask_logits is not None and tuple(mask_logits.shape) != (theta.shape[0], P * patch * patch):
+        raise ValueError(f'scene_patches: mask_logits must be (B, P*patch*patch), got {tuple(mask_logits.shape)}')
+    if noise is not None and tuple(noise.shape) != (patch, patch):
+        raise ValueError(f'scene_patches: noise must be (patch, patch), got {tuple(noise.shape)}')
+    return _ScenePatches.apply(theta, mask_logits, noise, int(patch), int(S))
+
+
 # =========================================================================== IQN / losses
 def iqn_cos_embed(taus, embedding_range):
     """cos((tau*pi)*range) -- no gradient (taus are sampled, range is a buffer)."""

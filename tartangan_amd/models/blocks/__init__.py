@@ -5,3 +5,4 @@ from .discriminator import (  # noqa
 from .generator import (  # noqa
     GeneratorInputMLP, GeneratorOutput, ResidualGeneratorBlock, TiledZGeneratorInput,
 )
+from .scene import SceneStructureBlock  # noqa

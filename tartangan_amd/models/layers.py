@@ -80,6 +80,15 @@ class Tanh(nn.Tanh):
         return TF.tanh(x)
 
 
+class Sigmoid(nn.Sigmoid):
+    """Parameter-free place holder that keeps the reference's ``Sequential(Linear, Sigmoid)`` layouts (state_dict keys
+    ``masks.0.*``, models/blocks/scene.py:103-106).  Its one user, ``SceneStructureBlock``, hands the Linear's raw output to
+    ``TF.scene_patches``, which evaluates the sigmoid inside the kernel; there is no stand-alone sigmoid kernel."""
+
+    def forward(self, x):
+        raise NotImplementedError('tartangan_amd.Sigmoid is fused into functional.scene_patches; it has no kernel of its own')
+
+
 class AvgPool2d(nn.AvgPool2d):
     def __init__(self, kernel_size, **kw):
         super().__init__(kernel_size, **kw)

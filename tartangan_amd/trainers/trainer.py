@@ -16,7 +16,7 @@ from .utils import set_device_from_args
 
 
 class RngFeed:
-    """Host-side random inputs of one step (latents z, IQN quantile fractions tau).
+    """Host-side random inputs of one step (latents z, IQN quantile fractions tau, the scene block's patch noise).
 
     The reference draws them from the CPU default generator inside the step and moves them
     to the device (trainer.py:153-156, models/iqn.py:105-108).  To replay the step from
@@ -24,7 +24,8 @@ class RngFeed:
     buffers, in exactly the reference's order.  The first (eager) step records that order;
     afterwards ``refill`` reproduces it.  Under data parallelism every rank draws the GLOBAL
     tensor from the same seed and keeps its own rows (tau rows are quantile-major:
-    row = q * B + b), so the union over ranks is the single-process stream.
+    row = q * B + b), so the union over ranks is the single-process stream.  Kind 'noise' is one (rows, cols) normal draw
+    shared by the whole batch (models/blocks/scene.py:139-140): identical on every rank, never sliced.
     """
 
     def __init__(self, device, rank=0, world=1):
@@ -43,6 +44,8 @@ class RngFeed:
         if kind == 'z':
             full = torch.randn(rows * self.world, cols)
             return full[self.rank * rows:(self.rank + 1) * rows]
+        if kind == 'noise':
+            return torch.randn(rows, cols)
         # tau: (Q*B_global, 1) with row = q*B_global + b  ->  this rank's (Q*B, 1)
         q = cols
         full = torch.rand(rows * self.world, 1)
@@ -50,7 +53,8 @@ class RngFeed:
         return full.view(q, b_local * self.world)[:, self.rank * b_local:(self.rank + 1) * b_local].reshape(rows, 1)
 
     def draw(self, kind, rows, cols):
-        """kind 'z': (rows, cols) normal;  kind 'tau': (rows, 1) uniform with cols = num_quantiles."""
+        """kind 'z': (rows, cols) normal;  kind 'tau': (rows, 1) uniform with cols = num_quantiles;  kind 'noise': (rows, cols)
+        normal, the same on every rank."""
         if self.mode == 'off':
             return self._draw_cpu(kind, rows, cols).contiguous().to(self.device)
         if self.mode == 'record':
@@ -74,7 +78,7 @@ class RngFeed:
         inputs with a single copy, and the latents lie back to back -- whatever else is drawn between them -- so that the two
         generator passes of a step run over them as one (2B, latent) tensor without joining them first (functional._join)."""
         self.plan = [tuple(p) for p in plan]
-        sizes = [rows * (cols if kind == 'z' else 1) for kind, rows, cols in self.plan]
+        sizes = [rows * (1 if kind == 'tau' else cols) for kind, rows, cols in self.plan]
         order = sorted(range(len(self.plan)), key=lambda i: (self.plan[i][0] != 'z', i))
         offsets, total = {}, 0
         for i in order:
@@ -85,7 +89,7 @@ class RngFeed:
         self._host_arena = host.pin_memory() if self._arena.is_cuda else host
         self.static, self.host = [], []
         for i, (kind, rows, cols) in enumerate(self.plan):
-            width = cols if kind == 'z' else 1
+            width = 1 if kind == 'tau' else cols
             self.static.append(self._arena[offsets[i]:offsets[i] + sizes[i]].view(rows, width))
             self.host.append(self._host_arena[offsets[i]:offsets[i] + sizes[i]].view(rows, width))
         self.cursor = 0
@@ -95,7 +99,7 @@ class RngFeed:
             if self.world == 1:
                 # straight into the pinned staging buffer: ``torch.randn(r, c)`` is ``empty(r, c).normal_()`` and
                 # ``torch.rand(r, 1)`` is ``empty(r, 1).uniform_()`` -- the same values from the same generator state
-                host.normal_() if kind == 'z' else host.uniform_()
+                host.uniform_() if kind == 'tau' else host.normal_()
             else:
                 host.copy_(self._draw_cpu(kind, rows, cols))
 
@@ -170,7 +174,7 @@ class Trainer:
         tensor, never part of the recorded plan, the same values on every rank."""
         if self._in_step:
             return self.rng_feed.draw(kind, rows, cols)
-        val = torch.randn(rows, cols) if kind == 'z' else torch.rand(rows, 1)
+        val = torch.rand(rows, 1) if kind == 'tau' else torch.randn(rows, cols)
         return val.to(self.device)
 
     def sample_g(self, n=None, target_g=False, **g_kwargs):
