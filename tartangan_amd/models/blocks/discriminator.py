@@ -18,6 +18,13 @@ _lrelu = functools.partial(LeakyReLU, 0.2)
 _half = functools.partial(interpolate, scale_factor=0.5, mode='bilinear', align_corners=True)
 
 
+def _is_half(fn):
+    """Is ``fn`` the default shortcut resampling?  By value, not identity: a block that went through ``torch.save`` /
+    ``torch.load`` or ``copy.deepcopy`` holds its own copy of the partial, and must keep the fused paths below."""
+    return fn is _half or (type(fn) is functools.partial and fn.func is _half.func and fn.args == _half.args
+                           and fn.keywords == _half.keywords)
+
+
 class DiscriminatorInput(nn.Module):
     """from-RGB 1x1 convolution"""
 
@@ -52,7 +59,7 @@ class ResidualDiscriminatorBlock(nn.Module):
         self.interpolate = interpolate
 
     def forward(self, x):
-        if self.interpolate is _half:
+        if _is_half(self.interpolate):
             shortcut, x = TF.fork_bilinear_half(x)      # one graph node for both uses of x (see functional._ForkBilinearHalf)
         else:
             shortcut = self.interpolate(x)
@@ -61,7 +68,7 @@ class ResidualDiscriminatorBlock(nn.Module):
         return run_layers(self.convs, x, residual=shortcut)          # x + h, the add fused into the avg-pool
 
     def default_resampling(self):
-        return self.interpolate is _half
+        return _is_half(self.interpolate)
 
     # ---- the first block fused with the from-RGB 1x1 convolution in front of it
     def fuses_with(self, rgb):
@@ -72,7 +79,7 @@ class ResidualDiscriminatorBlock(nn.Module):
         rc = list(getattr(rgb, 'convs', []))
         return (isinstance(rgb, DiscriminatorInput) and len(rc) == 1 and type(rc[0]) is Conv2d and rc[0].kernel_size == (1, 1)
                 and rc[0].bias is not None and len(mods) > 1 and type(mods[0]) is Conv2d and mods[0].kernel_size == (3, 3)
-                and self.project_input is None and self.interpolate is _half)
+                and self.project_input is None and _is_half(self.interpolate))
 
     def forward_from_rgb(self, img, rgb):
         """block(rgb(img)) with the two linear maps in front composed (discriminator.py:11-22 + :60-61: a 1x1 convolution

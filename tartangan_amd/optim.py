@@ -8,7 +8,10 @@ are views into it, their ``.grad``s views into a twin buffer), so Adam is one
 elementwise kernel, the EMA is one kernel, ``zero_grad`` is one fill and a
 data-parallel gradient all-reduce is one RCCL call on one bucket.
 """
+import itertools
 import math
+import operator
+import weakref
 
 import torch
 
@@ -40,23 +43,31 @@ def pack(tensors, like):
     return flat
 
 
+_PARAM_LISTS = weakref.WeakKeyDictionary()     # module -> cache entry; beside the module, not in it (pickling, deepcopy)
+
+
 def _param_list(module):
-    """``list(module.parameters())``, cached on the module: the recursive walk costs ~100 us for these networks, and a
-    replayed step checks its bindings several times."""
-    cached = module.__dict__.get('_tg_params')
+    """``list(module.parameters())``, cached: the recursive walk costs ~100 us for these networks, and a replayed step
+    checks its bindings several times.  A cached list is checked against the modules it came from on every use -- the values
+    of their ``_parameters`` dicts, by identity: ~60 pointer compares -- so a Parameter OBJECT replaced anywhere in the tree
+    (``conv.weight = nn.Parameter(...)``), or a parameter added to / removed from a module that owns parameters, is seen
+    at once.  A submodule swapped for another one, or a first parameter registered on a module that had none, changes none
+    of the dicts that are watched: the top-level counts and a fresh walk every 64 uses cover those."""
+    cached = _PARAM_LISTS.get(module)
     key = (len(module._modules), len(module._parameters))
-    if cached is not None and cached[0] == key and cached[2][0] < 64:
-        cached[2][0] += 1
-        return cached[1]
-    # (a Parameter OBJECT replaced deep inside the tree -- ``setattr(m, 'weight', new)``; ``module.to()`` and
-    # ``load_state_dict`` keep the objects -- is noticed at the latest after 64 uses, when the walk is taken again)
+    if cached is not None and cached[0] == key and cached[4][0] < 64:
+        seen = itertools.chain.from_iterable(map(dict.values, cached[2]))
+        if sum(map(len, cached[2])) == len(cached[3]) and all(map(operator.is_, seen, cached[3])):
+            cached[4][0] += 1
+            return cached[1]
+    owners = [m._parameters for m in module.modules() if m._parameters]
     params = list(module.parameters())
-    module.__dict__['_tg_params'] = (key, params, [0])
+    _PARAM_LISTS[module] = (key, params, owners, [p for d in owners for p in d.values()], [0])
     return params
 
 
 def invalidate_param_cache(module):
-    module.__dict__.pop('_tg_params', None)
+    _PARAM_LISTS.pop(module, None)
 
 
 def flatten_parameters(module):

@@ -103,8 +103,9 @@ class CNNTrainer(Trainer):
         if not getattr(self.args, 'pair_d', True):
             return False
         cached = getattr(self, '_pair_ok', None)
-        key = (id(self.d), self.data_parallel is not None and self.data_parallel.sync_bn)
-        if cached is not None and cached[0] == key:
+        # (the model itself, not its id: a model swapped in from outside can be handed the freed one's address)
+        key = (self.d, self.data_parallel is not None and self.data_parallel.sync_bn)
+        if cached is not None and cached[0][0] is key[0] and cached[0][1] == key[1]:
             return cached[1]
         ok = True
         for m in self.d.modules():
@@ -216,8 +217,8 @@ class CNNTrainer(Trainer):
         if not getattr(self.args, 'pair_g', True):
             return False
         cached = self.__dict__.get('_pair_g_ok')
-        key = (id(self.g), self.data_parallel is not None and self.data_parallel.sync_bn)
-        if cached is not None and cached[0] == key:
+        key = (self.g, self.data_parallel is not None and self.data_parallel.sync_bn)
+        if cached is not None and cached[0][0] is key[0] and cached[0][1] == key[1]:
             return cached[1]
         ok = isinstance(self.g.blocks[0], GeneratorInputMLP)
         for m in self.g.modules():
@@ -326,8 +327,11 @@ class CNNTrainer(Trainer):
         """Replay the step from captured HIP graphs (D phase | G forward | D Adam + D(fake) + G backward |
         G Adam + EMA; the middle two are one graph on a single GPU) instead of ~1500 eager launches.  The
         cuts are where a data-parallel run starts / joins the all-reduces of its gradient buckets.  Host-side RNG is pre-drawn by ``RngFeed`` in the reference's order, so
-        results are identical to eager mode.  The first call runs eagerly (recording the RNG plan),
-        the second captures, later calls only replay."""
+        results are identical to eager mode.  A stock trainer knows its draw order in advance (``RngFeed.adopt``): its
+        first call of a batch shape captures and replays, later calls of that shape only replay.  A subclass or foreign
+        models: the first call runs eagerly and records the order, the second captures.  A batch of another shape (a
+        ragged last batch) runs eagerly and leaves the graphs alone.  If the capture itself is refused, that call and
+        all later ones run eagerly (with a warning)."""
         if self.device == 'cpu':
             raise RuntimeError('HIP graphs need a ROCm device')
         self._graph_requested = True
@@ -403,27 +407,36 @@ class CNNTrainer(Trainer):
             # call 1 (the RNG plan is being recorded), or a batch of another shape than the plan / the captured graphs
             # (a ragged last batch): this call runs eagerly
             return self._train_batch_eager(imgs)
-        gen = (self.optimizer_d.ensure_bound(), self.optimizer_g.ensure_bound())
+        # what the graphs have baked in: these objects' buffers, as of these bucket generations.  (The objects themselves, not
+        # their ids: a model or optimiser swapped from outside -- a resume into a live trainer -- starts at generation 0 again.)
+        gen = (self.d, self.optimizer_d, self.optimizer_d.ensure_bound(), self.g, self.optimizer_g, self.optimizer_g.ensure_bound(),
+               self.target_g)
         if self._graphs is not None and gen != self._graph_gen:
-            self._graphs = None                                # parameter buckets were rebuilt: recapture
+            self._graphs = None                                # parameter buckets were rebuilt, or a model replaced: recapture
         dp = self.data_parallel
         if self._graphs is not None and dp is not None and dp.multi and dp.buckets_in_graph != self._buckets_in_graph:
             self._graphs = None                                # the collective schedule changed (autotune_overlap): recapture
-        if self._graphs is None:                               # call 2: capture (nothing executes yet)
+        if self._graphs is None:                               # capture (nothing executes yet)
+            # Whatever the captured passes only READ and keep beyond the step is built -- and executed -- out here: under
+            # capture its fill would be recorded, not run, and a capture that fails would leave the cached tensor
+            # uninitialised for the eager steps that follow.
+            self._labels(len(imgs))
+            labels_before = set(self.__dict__.get('_label_cache', ()))
             try:
                 self._capture(imgs)
                 self._graph_gen = gen
             except _be.KernelError:
+                self._drop_capture_leftovers(labels_before)
                 raise                                          # a tg_* call failed: a real error, never downgraded
             except RuntimeError as exc:                        # e.g. a collective library that refuses capture
-                if 'capture' not in str(exc).lower() and 'graph' not in str(exc).lower():
+                self._drop_capture_leftovers(labels_before)
+                # (HIP: "operation not permitted when stream is capturing"; torch: "... during capture", "CUDA graphs ...")
+                if 'captur' not in str(exc).lower() and 'graph' not in str(exc).lower():
                     raise
                 import warnings
                 warnings.warn(f'HIP-graph capture failed ({exc!r}); continuing in eager mode')
                 self._graph_requested = False
-                self._graphs = None
                 feed.cursor = 0
-                self.__dict__.pop('_fake_for_g_phase', None)
                 return self._train_batch_eager(imgs)           # consumes the values refill() drew for this step
         g1, g2a, g2b, g3 = self._graphs
         self._static_imgs.copy_(imgs, non_blocking=True)
@@ -444,6 +457,16 @@ class CNNTrainer(Trainer):
         self._finish_reduce('g')
         g3.replay()
         return self._out_losses
+
+    def _drop_capture_leftovers(self, labels_before=()):
+        """After an abandoned capture: nothing that was created while the stream was capturing may be read again (its
+        kernels were recorded, never run) -- label tensors of any other batch size than the pre-built one included."""
+        self._graphs = None
+        cache = self.__dict__.get('_label_cache', {})
+        for key in [k for k in cache if k not in labels_before]:
+            del cache[key]
+        for name in ('_fake_for_g_phase', '_static_imgs', '_out_d', '_out_g', '_out_losses'):
+            self.__dict__.pop(name, None)
 
     def _begin_reduce(self, key, optimizer):
         """Data-parallel hooks: start / join the averaging of a flat gradient bucket over the ranks (no-ops on 1 GPU)."""

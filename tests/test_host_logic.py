@@ -680,3 +680,158 @@ def test_composed_from_rgb_filter_and_its_gradients():
         loss.backward()
     for p, b in zip((w1, b1, w3), want):
         assert torch.allclose(p.grad, 1 + b, rtol=1e-4, atol=1e-5)
+
+
+# ----------------------------------------------------------------------------------------------- step transitions (host halves)
+# The graphed halves are tests/test_step_transitions_gpu.py.  Same rule here: the control runs the same kernel sequence on the
+# same inputs, so everything is compared for bit equality after every step.
+def _small_iqn_trainer(**extra):
+    cfg = GAN_CONFIGS['32']._replace(attention=(2,))
+    tr = IQNTrainer(IQNTrainer.default_args(config=cfg, batch_size=4, device='cpu', **extra))
+    torch.manual_seed(0)
+    tr.build_models()
+    tr.g.load_state_dict(procedural_state(tr.g.state_dict(), 7))
+    tr.target_g.load_state_dict(procedural_state(tr.target_g.state_dict(), 8))
+    tr.d.load_state_dict(procedural_state(tr.d.state_dict(), 9))
+    return tr
+
+
+def _full_state(tr, logs):
+    snap = dict(logs=dict(logs), step_count=(tr.optimizer_g.step_count, tr.optimizer_d.step_count))
+    for name, opt in (('optimizer_g', tr.optimizer_g), ('optimizer_d', tr.optimizer_d)):
+        for key in ('flat', 'exp_avg', 'exp_avg_sq'):
+            snap[f'{name}.{key}'] = getattr(opt, key).clone()
+    for name, net in (('d', tr.d), ('g', tr.g), ('target_g', tr.target_g)):
+        for key, value in net.state_dict().items():
+            snap[f'{name}.{key}'] = value.clone()
+    return snap
+
+
+def _run_steps(tr, sizes, before=None, seed=31):
+    """``before``: {step index: fn(trainer)} -> (complete state after every step, host RNG position at the end)."""
+    torch.manual_seed(seed)
+    snaps = []
+    for k, bs in enumerate(sizes):
+        if before and k in before:
+            before[k](tr)
+        snaps.append(_full_state(tr, tr.train_batch(synthetic_images(4, 32, 50 + k)[:bs])))
+    return snaps, float(torch.rand(1))
+
+
+def _assert_bit_identical(got, want):
+    assert got[1] == want[1]                                         # host RNG consumed alike
+    assert len(got[0]) == len(want[0])
+    for k, (a, b) in enumerate(zip(got[0], want[0])):
+        assert a['logs'] == b['logs'], (k, a['logs'], b['logs'])
+        assert a['step_count'] == b['step_count'], k
+        assert a.keys() == b.keys()
+        for key in a:
+            if key not in ('logs', 'step_count'):
+                assert torch.equal(a[key], b[key]), (k, key)
+
+
+def _stride2_conv_deep_in_d(tr):
+    from tartangan_amd.models.blocks import ResidualDiscriminatorBlock
+    block = [m for m in tr.d.blocks if isinstance(m, ResidualDiscriminatorBlock)][-1]
+    conv = block.convs[len(block.convs) - 2]
+    assert tuple(conv.weight.shape[2:]) == (3, 3)
+    return conv
+
+
+def test_replaced_parameter_object_is_rehomed_at_the_next_step(single_thread):
+    """``conv.weight = nn.Parameter(...)`` deep inside D between two steps (the control scales the same weight in place): the
+    cached parameter list notices at once, the new object becomes a view of the bucket and is the one Adam steps."""
+    from tartangan_amd.optim import _is_bound, _param_list
+    tr, control = _small_iqn_trainer(), _small_iqn_trainer()
+    seen = {}
+
+    def replace(t):
+        conv = _stride2_conv_deep_in_d(t)
+        seen['generation'] = t.optimizer_d.generation
+        assert any(p is conv.weight for p in _param_list(t.d))       # (the list is cached by now, with the old object in it)
+        conv.weight = torch.nn.Parameter(conv.weight.detach() * 0.5)
+        seen['new'] = conv.weight
+
+    def scale_in_place(t):
+        with torch.no_grad():
+            _stride2_conv_deep_in_d(t).weight.mul_(0.5)
+
+    def rehomed(t):
+        opt, w = t.optimizer_d, _stride2_conv_deep_in_d(t).weight
+        assert w is seen['new'] and any(p is w for p in _param_list(t.d))
+        assert _is_bound(list(t.d.parameters()), opt.flat, opt.grads)
+        assert opt.generation == seen['generation'] + 1
+        assert w.grad is not None and float(w.grad.abs().max()) > 0   # trained in the step just taken
+
+    got = _run_steps(tr, [4] * 5, {2: replace, 3: rehomed})
+    _assert_bit_identical(got, _run_steps(control, [4] * 5, {2: scale_in_place}))
+
+
+def test_parameter_list_cache_sees_every_change_of_the_parameter_set():
+    """Unit half of the above: a replaced, added or removed Parameter is seen by the very next use; an untouched module is
+    served from the cache (the same list object: no walk)."""
+    from tartangan_amd.optim import _param_list
+    net = torch.nn.Sequential(torch.nn.Sequential(torch.nn.Conv2d(3, 4, 3), torch.nn.Conv2d(4, 4, 3)), torch.nn.Linear(4, 2))
+    first = _param_list(net)
+    assert _param_list(net) is first and [id(p) for p in first] == [id(p) for p in net.parameters()]
+    net[0][1].weight = torch.nn.Parameter(net[0][1].weight.detach().clone())
+    assert [id(p) for p in _param_list(net)] == [id(p) for p in net.parameters()]
+    net[0][0].register_parameter('extra', torch.nn.Parameter(torch.zeros(3)))
+    assert [id(p) for p in _param_list(net)] == [id(p) for p in net.parameters()]
+    net[0][0].bias = None
+    assert [id(p) for p in _param_list(net)] == [id(p) for p in net.parameters()]
+    shared = torch.nn.Linear(4, 2)
+    shared.bias = net[1].bias                                        # one Parameter under two owners is listed once
+    both = torch.nn.ModuleList([net, shared])
+    assert [id(p) for p in _param_list(both)] == [id(p) for p in both.parameters()]
+    assert not any(k.startswith('_tg_param') for m in both.modules() for k in m.__dict__)
+
+
+def test_pickled_discriminator_carries_no_cache_and_trains_on(tmp_path, single_thread):
+    """``torch.save(tr.d)`` / ``torch.load`` after step 2: no cached parameter list travels in the file, and the loaded module
+    -- handed to a fresh FusedAdam that takes over the old one's state, and put in the trainer's place -- trains on exactly
+    like the undisturbed control."""
+    from tartangan_amd.optim import FusedAdam
+    tr, control = _small_iqn_trainer(), _small_iqn_trainer()
+
+    def swap(t):
+        path = f'{tmp_path}/d.pt'
+        torch.save(t.d, path)
+        back = torch.load(path, weights_only=False)
+        assert all('_tg_params' not in m.__dict__ for m in back.modules())
+        assert all(m.default_resampling() for m in back.modules() if hasattr(m, 'default_resampling'))    # (fused paths kept)
+        assert all('_tg_params' not in m.__dict__ for m in t.d.modules())
+        old = t.optimizer_d
+        opt = FusedAdam(back, lr=old.lr, betas=old.betas, eps=old.eps)
+        opt.load_state_dict(old.state_dict())
+        t.d, t.optimizer_d = back, opt
+
+    got = _run_steps(tr, [4] * 5, {2: swap})
+    _assert_bit_identical(got, _run_steps(control, [4] * 5))
+
+
+def test_ragged_batch_switches_the_rng_feed_off_for_one_call(single_thread):
+    """4, 4, 3, 4, 4 images without graphs: the RngFeed serves its pre-drawn plan, steps aside for the batch of another shape
+    (inline draws), and serves again -- against a trainer that draws everything inline, in every step.  (Both with
+    ``pair_g=False``: a served plan lets the generator's two forwards share one pass, which inline draws cannot, and that
+    would be another kernel sequence.)"""
+    tr, control = _small_iqn_trainer(pair_g=False), _small_iqn_trainer(pair_g=False)
+    control._known_rng_plan = lambda bs: None                        # never adopt a plan ...
+    plain = control.train_batch
+
+    def inline_draws(imgs):
+        feed = control.rng_feed
+        feed.plan.clear(); feed.static.clear(); feed.host.clear()    # ... and forget the recorded one: every step records = draws inline
+        feed.key = None
+        return plain(imgs)
+
+    control.train_batch = inline_draws
+    modes = {id(tr): [], id(control): []}
+    for t in (tr, control):
+        t._d_phase = lambda imgs, _t=t, _orig=t._d_phase: (modes[id(_t)].append(_t.rng_feed.mode), _orig(imgs))[1]
+    sizes = [4, 4, 3, 4, 4]
+    got = _run_steps(tr, sizes)
+    want = _run_steps(control, sizes)
+    assert modes[id(tr)] == ['serve', 'serve', 'off', 'serve', 'serve']
+    assert modes[id(control)] == ['record'] * 5
+    _assert_bit_identical(got, want)
