@@ -283,6 +283,14 @@ int tg_pool2(const float* x, const float* residual /*nullable: y = residual + po
 int tg_bilinear_half_fwd(const float* x, float* y, int BC, int H, int W, void* stream);
 int tg_bilinear_half_bwd(const float* gy, const float* residual /*nullable, shape of gx*/, float* gx,
                          int BC, int H, int W, void* stream);
+/* F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) models/shared/blocks.py:64-67 (since version 102)
+ * x (BC, H, W) -> y (BC, 2H, 2W) [+ residual, shape of y]; same fp32 source-index arithmetic as the half-size pair
+ * (scale = (in - 1) / (out - 1), 0 for in = 1), so _bwd is the exact transpose of _fwd: gy (BC, 2H, 2W) -> gx (BC, H, W)
+ * [+ residual, shape of gx], gather form, fixed summation order, no atomics: two runs are bit-identical.
+ * H, W are the dims of the SMALL side for both; any H, W in 1 .. 16384 (TG_EUNSUPPORTED above), pointers at any multiple of
+ * 4 bytes (16-byte rows are written where the alignment allows); no workspace.                                        */
+int tg_bilinear_up2x_fwd(const float* x, const float* residual /*nullable*/, float* y, int BC, int H, int W, void* stream);
+int tg_bilinear_up2x_bwd(const float* gy, const float* residual /*nullable*/, float* gx, int BC, int H, int W, void* stream);
 /* Input side of the FID / Inception-score pipeline (8f-2).  out (B, C, OH, OW) = bilinear resize (align_corners=True;
  * F.interpolate(x, size=(299, 299), mode='bilinear', align_corners=True), inception_utils.py:49-50) of x (B, C, H, W) after
  * `stages` applications of  x <- ((x + 1) / 2 - mean[c]) / std[c]  -- one in WrapInception.forward (inception_utils.py:44-47), a
@@ -344,6 +352,15 @@ int tg_fill(float* x, float value, int64_t n, void* stream);
  * the all-ones channel that carries the from-RGB bias when discriminator.py:11-22 (1x1) is composed into the first 3x3
  * (blocks/discriminator.py forward_from_rgb; replaces torch.cat + ones); Cd < Cs: its transpose (drop the channel). */
 int tg_copy_channels(const float* src, float* dst, int B, int Cs, int Cd, int HW, float fill, void* stream);
+/* The shared filter bank (models/shared/blocks.py:124-127, since version 102): every 3x3 convolution of a network reads
+ * filters.narrow(0, 0, O).narrow(1, 0, I) of ONE parameter bank [Omax][Imax][taps] (taps = kh * kw).
+ *   tg_filter_narrow      view [O][I][taps] <- that corner of the bank, as the dense filter the convolution kernels take
+ *   tg_filter_narrow_bwd  accumulate = 0: gbank is written completely -- the corner from gview, exact zeros elsewhere;
+ *                         accumulate = 1: gbank's corner += gview, every other element is neither read nor written.
+ * O <= Omax and I <= Imax, or TG_EINVAL.  Launches on one stream add in launch order: a deterministic sum.                */
+int tg_filter_narrow(const float* bank, float* view, int O, int I, int Omax, int Imax, int taps, void* stream);
+int tg_filter_narrow_bwd(const float* gview, float* gbank, int O, int I, int Omax, int Imax, int taps, int accumulate,
+                         void* stream);
 
 /* ---------------------------------------------------------------- softmax (attention.py:32) */
 int tg_softmax_fwd(const float* s, float* y, int rows, int cols, void* stream);

@@ -1,6 +1,7 @@
 // Resampling kernels (all HBM-bound, gather form, no atomics):
 //   up2x / pool2            nearest x2 upsample <-> 2x2 sum-pool (transposes of each other)
 //   bilinear_half fwd/bwd   F.interpolate(scale .5, bilinear, align_corners=True) and its transpose
+//   bilinear_up2x fwd/bwd   F.interpolate(scale 2, bilinear, align_corners=True) and its transpose (shared-filter generator)
 //   maxpool2 fwd/bwd/gather 2x2 max-pool with argmax byte, scatter and gather by argmax
 #include "common.h"
 
@@ -244,6 +245,254 @@ __global__ void __launch_bounds__(RS_BLOCK) bilinear_half_bwd_onehit_kernel(cons
   }
 }
 
+// ------------------------------------------------------------------ bilinear x2 (align_corners = True)
+// models/shared/blocks.py:64-67.  H x W -> 2H x 2W with the source-index arithmetic of `src_index` (scale = (in - 1) / (out - 1) < 1/2).
+// Both directions walk ROWS of the flattened (plane, row) index: a workgroup iteration covers a SLAB of consecutive rows,
+// 1 << shift threads per row (the smallest power of two that covers a row's units, at most the workgroup), a unit being four
+// consecutive elements (VEC: one 16-byte store) or one.
+// MEASURED on the first form of these kernels (every operand gathered from global memory, 8 / up to 36 single-float loads per
+// element): the time followed the NUMBER of gather instructions (~60 cycles per wave and load) and not the bytes -- 2.0 TB/s forward,
+// 0.7 TB/s for the transpose.  So the rows a slab reads -- consecutive rows of the other side, one contiguous piece of memory -- are
+// staged in LDS with 16-byte loads, and the gathers run on LDS.  The per-axis (index, weight) tables are built once per workgroup.
+// Sizes beyond the tables (forward W > 512; transpose H or W > 256) take the `direct` kernels: entries computed in place, gathers
+// from global memory.
+constexpr int BU_MAX_IN = 512;       // forward: columns with a table entry (2 * BU_MAX_IN outputs)
+constexpr int BU_ROWS = 4;           // forward: output rows per thread and iteration
+constexpr int BU_TILE = 3072;        // forward: staged input floats, >= (slab / 2 + 4) * W for every W <= BU_MAX_IN (host-checked)
+constexpr int BUB_MAX_IN = 256;      // transpose: rows / columns with a table entry
+constexpr int BUB_TILE = 7168;       // transpose: staged gy floats, >= (2 * slab + 6) * 2W for every W <= BUB_MAX_IN (host-checked)
+
+__device__ __forceinline__ int64_t row_div(int64_t r, int d) {          // r / d; 32-bit where it fits (a 64-bit divide is ~4x the work)
+  return (r >> 31) == 0 ? (int64_t)((uint32_t)r / (uint32_t)d) : r / d;
+}
+
+// n contiguous floats, global -> LDS; 16-byte loads when `vec` (source 16-byte aligned and n a multiple of 4)
+__device__ __forceinline__ void stage_rows(float* __restrict__ tile, const float* __restrict__ src, int n, bool vec) {
+  if (vec) {
+    for (int i = threadIdx.x; i < (n >> 2); i += RS_BLOCK) reinterpret_cast<float4*>(tile)[i] = reinterpret_cast<const float4*>(src)[i];
+  } else {
+    for (int i = threadIdx.x; i < n; i += RS_BLOCK) tile[i] = src[i];
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store_unit(float* __restrict__ dst, const float* __restrict__ residual, int64_t off, const float* o) {
+  if (VEC) {
+    float4 v = make_float4(o[0], o[VEC ? 1 : 0], o[VEC ? 2 : 0], o[VEC ? 3 : 0]);
+    if (residual) {
+      const float4 q = *reinterpret_cast<const float4*>(residual + off);
+      v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+    }
+    *reinterpret_cast<float4*>(dst + off) = v;
+  } else {
+    dst[off] = residual ? residual[off] + o[0] : o[0];
+  }
+}
+
+// Output rows [R0, R1) of the flattened index r = bc * 2H + oh read the flattened input rows bc * H + i0(oh) .. bc * H + i1(oh).
+// With s < 1/2 and 1/2 - s = 1 / (2 (2H - 1)):  r / 2 - 2 < bc * H + floor(s * oh) <= r / 2, so a slab of n rows reads at most
+// n / 2 + 4 consecutive input rows.
+template <bool VEC>
+__global__ void __launch_bounds__(RS_BLOCK) bilinear_up2x_fwd_kernel(const float* __restrict__ x, const float* __restrict__ residual,
+                                                                     float* __restrict__ y, int64_t nrows /* BC * 2H */, int H, int W,
+                                                                     float sh, float sw, int shift, int xvec) {
+  constexpr int U = VEC ? 4 : 1;
+  const int OH = 2 * H, OW = 2 * W, units = OW / U;
+  __shared__ Lerp cols[2 * BU_MAX_IN];
+  __shared__ __align__(16) float tile[BU_TILE];
+  for (int i = threadIdx.x; i < OW; i += RS_BLOCK) cols[i] = src_index(i, sw, W);
+  const int tpr = 1 << shift, lane = threadIdx.x & (tpr - 1), rsub = threadIdx.x >> shift, rpb = RS_BLOCK >> shift;
+  const int slab = rpb * BU_ROWS, cap_rows = BU_TILE / W;
+  for (int64_t R0 = blockIdx.x * (int64_t)slab; R0 < nrows; R0 += gridDim.x * (int64_t)slab) {
+    const int64_t R1 = R0 + slab < nrows ? R0 + slab : nrows;
+    const int64_t bc_first = row_div(R0, OH), bc_last = row_div(R1 - 1, OH);
+    const int64_t in_first = bc_first * H + src_index((int)(R0 - bc_first * OH), sh, H).i0;
+    const int64_t in_last = bc_last * H + src_index((int)(R1 - 1 - bc_last * OH), sh, H).i1;
+    int in_rows = (int)(in_last - in_first) + 1;
+    in_rows = in_rows < cap_rows ? in_rows : cap_rows;       // (never binds: see the bound above)
+    __syncthreads();                                         // the previous slab's readers are done (first pass: the table is built)
+    stage_rows(tile, x + in_first * W, in_rows * W, xvec);
+    __syncthreads();
+    Lerp a[BU_ROWS];
+    int t0[BU_ROWS], t1[BU_ROWS];
+#pragma unroll
+    for (int j = 0; j < BU_ROWS; ++j) {
+      int64_t r = R0 + rsub + (int64_t)j * rpb;
+      r = r < R1 ? r : R1 - 1;                               // (a row past the slab computes its last row again and stores nothing)
+      const int64_t bc = row_div(r, OH);
+      a[j] = src_index((int)(r - bc * OH), sh, H);
+      int d0 = (int)(bc * H + a[j].i0 - in_first), d1 = (int)(bc * H + a[j].i1 - in_first);
+      d0 = d0 < in_rows ? d0 : in_rows - 1; d1 = d1 < in_rows ? d1 : in_rows - 1;
+      t0[j] = d0 * W; t1[j] = d1 * W;
+    }
+    for (int u = lane; u < units; u += tpr) {
+      float o[BU_ROWS][U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const Lerp b = cols[u * U + k];
+#pragma unroll
+        for (int j = 0; j < BU_ROWS; ++j) {
+          const float top = b.l0 * tile[t0[j] + b.i0] + b.l1 * tile[t0[j] + b.i1];
+          const float bot = b.l0 * tile[t1[j] + b.i0] + b.l1 * tile[t1[j] + b.i1];
+          o[j][k] = a[j].l0 * top + a[j].l1 * bot;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < BU_ROWS; ++j) {
+        const int64_t r = R0 + rsub + (int64_t)j * rpb;
+        if (r < R1) store_unit<VEC>(y, residual, r * OW + (int64_t)u * U, o[j]);
+      }
+    }
+  }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(RS_BLOCK) bilinear_up2x_fwd_direct_kernel(const float* __restrict__ x, const float* __restrict__ residual,
+                                                                            float* __restrict__ y, int64_t nrows, int H, int W,
+                                                                            float sh, float sw, int shift) {
+  constexpr int U = VEC ? 4 : 1;
+  const int OH = 2 * H, OW = 2 * W, units = OW / U;
+  const int tpr = 1 << shift, lane = threadIdx.x & (tpr - 1), rpb = RS_BLOCK >> shift;
+  for (int64_t r = blockIdx.x * (int64_t)rpb + (threadIdx.x >> shift); r < nrows; r += gridDim.x * (int64_t)rpb) {
+    const int64_t bc = row_div(r, OH);
+    const Lerp a = src_index((int)(r - bc * OH), sh, H);
+    const float* p0 = x + (bc * H + a.i0) * (int64_t)W;
+    const float* p1 = x + (bc * H + a.i1) * (int64_t)W;
+    for (int u = lane; u < units; u += tpr) {
+      float o[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const Lerp b = src_index(u * U + k, sw, W);
+        const float top = b.l0 * p0[b.i0] + b.l1 * p0[b.i1];
+        const float bot = b.l0 * p1[b.i0] + b.l1 * p1[b.i1];
+        o[k] = a.l0 * top + a.l1 * bot;
+      }
+      store_unit<VEC>(y, residual, r * OW + (int64_t)u * U, o);
+    }
+  }
+}
+
+// The transpose, gather form.  Input index i receives from every output o with floor(scale * o) in {i - 1, i}: a window of
+// 2 / scale = 4 + 2 / (in - 1) outputs, up to SIX of them (in = 2; five from in = 3 on, six again where fp32 rounds scale * o
+// below an integer), starting at the first output whose floor index reaches i - 1.  That start is found exactly, by stepping a
+// safe underestimate forward with the forward's own arithmetic; it lies in [2 (i - 1), 2 (i - 1) + 2].
+struct Axis6 { int lo; float w[6]; int pad; };          // 32 bytes
+__device__ __forceinline__ Axis6 axis6(int in, float sc, int in_size, int out_size) {
+  Axis6 e;
+  int lo = sc > 0.f ? (int)((float)(in - 1) / sc) - 1 : 0;
+  lo = lo < 0 ? 0 : lo;
+  while (lo < out_size - 1 && src_index(lo, sc, in_size).i0 < in - 1) ++lo;
+  e.lo = lo;
+#pragma unroll
+  for (int u = 0; u < 6; ++u) e.w[u] = (lo + u < out_size) ? axis_weight(lo + u, in, sc, in_size) : 0.f;
+  e.pad = 0;
+  return e;
+}
+
+// Input rows [R0, R1) of the flattened index r = bc * H + h read the flattened gy rows 2r - 2 .. 2r + 5 at most (clipped to the
+// plane): a slab of n rows reads at most 2n + 6 consecutive rows of gy.  The map is separable, and so is the kernel: the staged
+// rows are first reduced along the columns (mid[row][w] = sum_t wc[w][t] * gy[row][lo(w) + t]: neighbouring lanes read neighbouring
+// windows, two floats apart), then along the rows (gx[h][w] = sum_a wr[h][a] * mid[lo(h) + a][w]: 16-byte LDS reads) -- 18 LDS reads
+// per element instead of the 36 of the direct double sum, whose four-column threads sat eight floats apart on the same banks.
+// Same summation order as the direct kernel.  Every candidate is READ (from a row / column clamped into the window's plane) and
+// the ones outside the window enter with their weight of exactly zero: no branch per candidate, and adding +-0 changes no finite sum.
+template <bool VEC>
+__global__ void __launch_bounds__(RS_BLOCK) bilinear_up2x_bwd_kernel(const float* __restrict__ gy, const float* __restrict__ residual,
+                                                                     float* __restrict__ gx, int64_t nrows /* BC * H */, int H, int W,
+                                                                     float sh, float sw, int shift, int gvec) {
+  constexpr int U = VEC ? 4 : 1;
+  const int OH = 2 * H, OW = 2 * W, units = W / U;
+  __shared__ Axis6 rows[BUB_MAX_IN], cols[BUB_MAX_IN];
+  __shared__ __align__(16) float tile[BUB_TILE];
+  __shared__ __align__(16) float mid[BUB_TILE / 2];
+  for (int i = threadIdx.x; i < H + W; i += RS_BLOCK) {
+    if (i < H) rows[i] = axis6(i, sh, H, OH);
+    else cols[i - H] = axis6(i - H, sw, W, OW);
+  }
+  __syncthreads();
+  const int tpr = 1 << shift, lane = threadIdx.x & (tpr - 1), rsub = threadIdx.x >> shift, slab = RS_BLOCK >> shift;
+  const int cap_rows = BUB_TILE / OW;
+  for (int64_t R0 = blockIdx.x * (int64_t)slab; R0 < nrows; R0 += gridDim.x * (int64_t)slab) {
+    const int64_t R1 = R0 + slab < nrows ? R0 + slab : nrows;
+    const int64_t bc_first = row_div(R0, H), bc_last = row_div(R1 - 1, H);
+    const int64_t g_first = bc_first * OH + rows[(int)(R0 - bc_first * H)].lo;
+    int last = rows[(int)(R1 - 1 - bc_last * H)].lo + 5;
+    last = last < OH ? last : OH - 1;
+    int g_rows = (int)(bc_last * OH + last - g_first) + 1;
+    g_rows = g_rows < cap_rows ? g_rows : cap_rows;          // (never binds: see the bound above)
+    __syncthreads();                                         // the previous slab's readers are done
+    stage_rows(tile, gy + g_first * OW, g_rows * OW, gvec);
+    __syncthreads();
+    for (int i = threadIdx.x; i < g_rows * W; i += RS_BLOCK) {
+      const int row = (int)((uint32_t)i / (uint32_t)W), w = i - row * W;
+      const Axis6 c = cols[w];
+      const float* grow = tile + row * OW;
+      float racc = 0.f;
+#pragma unroll
+      for (int t = 0; t < 6; ++t) racc += c.w[t] * grow[c.lo + t < OW ? c.lo + t : OW - 1];
+      mid[i] = racc;
+    }
+    __syncthreads();
+    const int64_t r = R0 + rsub;
+    if (r < R1) {
+      const int64_t bc = row_div(r, H);
+      const Axis6 ra = rows[(int)(r - bc * H)];
+      const int base = (int)(bc * OH + ra.lo - g_first);      // staged row of the window's first candidate
+      int mrow[6];
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        int row = base + (ra.lo + a < OH ? a : OH - 1 - ra.lo);
+        mrow[a] = (row < g_rows ? row : g_rows - 1) * W;
+      }
+      for (int u = lane; u < units; u += tpr) {
+        float o[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) o[k] = 0.f;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+#pragma unroll
+          for (int k = 0; k < U; ++k) o[k] += ra.w[a] * mid[mrow[a] + u * U + k];
+        }
+        store_unit<VEC>(gx, residual, r * W + (int64_t)u * U, o);
+      }
+    }
+  }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(RS_BLOCK) bilinear_up2x_bwd_direct_kernel(const float* __restrict__ gy, const float* __restrict__ residual,
+                                                                            float* __restrict__ gx, int64_t nrows, int H, int W,
+                                                                            float sh, float sw, int shift) {
+  constexpr int U = VEC ? 4 : 1;
+  const int OH = 2 * H, OW = 2 * W, units = W / U;
+  const int tpr = 1 << shift, lane = threadIdx.x & (tpr - 1), rpb = RS_BLOCK >> shift;
+  for (int64_t r = blockIdx.x * (int64_t)rpb + (threadIdx.x >> shift); r < nrows; r += gridDim.x * (int64_t)rpb) {
+    const int64_t bc = row_div(r, H);
+    const Axis6 ra = axis6((int)(r - bc * H), sh, H, OH);
+    const float* g = gy + bc * (int64_t)OH * OW + (int64_t)ra.lo * OW;
+    for (int u = lane; u < units; u += tpr) {
+      float o[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const Axis6 c = axis6(u * U + k, sw, W, OW);
+        float acc = 0.f;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          if (ra.w[a] == 0.f) continue;                      // (a zero weight marks a candidate outside the window or the plane)
+          const float* grow = g + (int64_t)a * OW + c.lo;
+          float racc = 0.f;
+#pragma unroll
+          for (int t = 0; t < 6; ++t)
+            if (c.w[t] != 0.f) racc += c.w[t] * grow[t];
+          acc += ra.w[a] * racc;
+        }
+        o[k] = acc;
+      }
+      store_unit<VEC>(gx, residual, r * W + (int64_t)u * U, o);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ 2x2 max pool
 __global__ void __launch_bounds__(RS_BLOCK) maxpool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                 uint8_t* __restrict__ idx, int64_t nout, int H, int W) {
@@ -404,6 +653,60 @@ int tg_bilinear_half_bwd(const float* gy, const float* residual, float* gx, int 
   }
   bilinear_half_bwd_kernel<<<tg_ew_grid(nin, RS_BLOCK), RS_BLOCK, 0, tg_stream(stream)>>>(gy, residual, gx, nin, H, W, OH, OW,
                                                                                          ac_scale(H, OH), ac_scale(W, OW));
+  return tg_launch_status();
+}
+
+// rows of `units` units each: threads per row (as a shift) and the grid of the bilinear x2 kernels
+static inline int up2x_shift(int units) {
+  int shift = 0;
+  while ((1 << shift) < units && shift < 8) ++shift;
+  return shift;
+}
+static inline int up2x_grid(int64_t nrows, int shift, int rows_per_thread) {
+  const int64_t slab = (int64_t)(RS_BLOCK >> shift) * rows_per_thread, g = (nrows + slab - 1) / slab;
+  return (int)(g < 2048 ? g : 2048);
+}
+constexpr int BU_MAX_DIM = 1 << 14;           // (2H)(2W) and every row offset inside a plane stay inside an int
+
+int tg_bilinear_up2x_fwd(const float* x, const float* residual, float* y, int BC, int H, int W, void* stream) {
+  TG_CHECK_PTR(x); TG_CHECK_PTR(y); TG_CHECK_POS(BC); TG_CHECK_POS(H); TG_CHECK_POS(W);
+  if (H > BU_MAX_DIM || W > BU_MAX_DIM) return TG_EUNSUPPORTED;
+  hipStream_t st = tg_stream(stream);
+  const int64_t nrows = (int64_t)BC * 2 * H;
+  const float sh = ac_scale(H, 2 * H), sw = ac_scale(W, 2 * W);
+  const bool vec = W % 2 == 0 && tg_aligned16(y) && (!residual || tg_aligned16(residual));
+  const int shift = up2x_shift(vec ? W / 2 : 2 * W);
+  const int slab = (RS_BLOCK >> shift) * BU_ROWS;
+  if (W <= BU_MAX_IN && (int64_t)(slab / 2 + 4) * W <= BU_TILE) {
+    const int grid = up2x_grid(nrows, shift, BU_ROWS), xvec = W % 4 == 0 && tg_aligned16(x);
+    if (vec) bilinear_up2x_fwd_kernel<true><<<grid, RS_BLOCK, 0, st>>>(x, residual, y, nrows, H, W, sh, sw, shift, xvec);
+    else bilinear_up2x_fwd_kernel<false><<<grid, RS_BLOCK, 0, st>>>(x, residual, y, nrows, H, W, sh, sw, shift, xvec);
+  } else {
+    const int grid = up2x_grid(nrows, shift, 1);
+    if (vec) bilinear_up2x_fwd_direct_kernel<true><<<grid, RS_BLOCK, 0, st>>>(x, residual, y, nrows, H, W, sh, sw, shift);
+    else bilinear_up2x_fwd_direct_kernel<false><<<grid, RS_BLOCK, 0, st>>>(x, residual, y, nrows, H, W, sh, sw, shift);
+  }
+  return tg_launch_status();
+}
+
+int tg_bilinear_up2x_bwd(const float* gy, const float* residual, float* gx, int BC, int H, int W, void* stream) {
+  TG_CHECK_PTR(gy); TG_CHECK_PTR(gx); TG_CHECK_POS(BC); TG_CHECK_POS(H); TG_CHECK_POS(W);
+  if (H > BU_MAX_DIM || W > BU_MAX_DIM) return TG_EUNSUPPORTED;
+  hipStream_t st = tg_stream(stream);
+  const int64_t nrows = (int64_t)BC * H;
+  const float sh = ac_scale(H, 2 * H), sw = ac_scale(W, 2 * W);
+  const bool vec = W % 4 == 0 && tg_aligned16(gx) && (!residual || tg_aligned16(residual));
+  const int shift = up2x_shift(vec ? W / 4 : W);
+  const int slab = RS_BLOCK >> shift;
+  if (H <= BUB_MAX_IN && W <= BUB_MAX_IN && (int64_t)(2 * slab + 6) * 2 * W <= BUB_TILE) {
+    const int grid = up2x_grid(nrows, shift, 1), gvec = W % 2 == 0 && tg_aligned16(gy);
+    if (vec) bilinear_up2x_bwd_kernel<true><<<grid, RS_BLOCK, 0, st>>>(gy, residual, gx, nrows, H, W, sh, sw, shift, gvec);
+    else bilinear_up2x_bwd_kernel<false><<<grid, RS_BLOCK, 0, st>>>(gy, residual, gx, nrows, H, W, sh, sw, shift, gvec);
+  } else {
+    const int grid = up2x_grid(nrows, shift, 1);
+    if (vec) bilinear_up2x_bwd_direct_kernel<true><<<grid, RS_BLOCK, 0, st>>>(gy, residual, gx, nrows, H, W, sh, sw, shift);
+    else bilinear_up2x_bwd_direct_kernel<false><<<grid, RS_BLOCK, 0, st>>>(gy, residual, gx, nrows, H, W, sh, sw, shift);
+  }
   return tg_launch_status();
 }
 

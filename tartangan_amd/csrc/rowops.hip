@@ -181,6 +181,34 @@ __global__ void __launch_bounds__(RB) attn_dbwd_rows_kernel(float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------ shared filter bank (models/shared/blocks.py:124-127)
+// view [O][I][taps] <-> the leading corner of bank [Omax][Imax][taps]: row o of the view is one contiguous run of I * taps floats
+// at bank + o * Imax * taps.  Plain copies / adds, one element per thread and iteration; no table of pointers.
+__global__ void __launch_bounds__(RB) filter_narrow_kernel(const float* __restrict__ bank, float* __restrict__ view, int64_t total,
+                                                           int64_t row /* I * taps */, int64_t bank_row /* Imax * taps */) {
+  for (int64_t i = blockIdx.x * (int64_t)RB + threadIdx.x; i < total; i += gridDim.x * (int64_t)RB) {
+    const int64_t o = i / row;
+    view[i] = bank[o * bank_row + (i - o * row)];
+  }
+}
+// accumulate = 0: the whole bank is written (the corner from gview, exact zeros elsewhere)
+__global__ void __launch_bounds__(RB) filter_narrow_bwd_fill_kernel(const float* __restrict__ gview, float* __restrict__ gbank, int64_t total,
+                                                                    int O, int64_t row, int64_t bank_row) {
+  for (int64_t i = blockIdx.x * (int64_t)RB + threadIdx.x; i < total; i += gridDim.x * (int64_t)RB) {
+    const int64_t o = i / bank_row, rem = i - o * bank_row;
+    gbank[i] = (o < O && rem < row) ? gview[o * row + rem] : 0.f;
+  }
+}
+// accumulate = 1: the corner is added to, nothing else is touched
+__global__ void __launch_bounds__(RB) filter_narrow_bwd_add_kernel(const float* __restrict__ gview, float* __restrict__ gbank, int64_t total,
+                                                                   int64_t row, int64_t bank_row) {
+  for (int64_t i = blockIdx.x * (int64_t)RB + threadIdx.x; i < total; i += gridDim.x * (int64_t)RB) {
+    const int64_t o = i / row;
+    float* dst = gbank + o * bank_row + (i - o * row);
+    *dst = *dst + gview[i];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -258,6 +286,30 @@ int tg_attn_dbwd_rows(float* s, const float* lse, float* gp, float* u, float* v,
   const bool vec = (cols % 4 == 0) && tg_aligned16(s) && tg_aligned16(gp) && tg_aligned16(u) && tg_aligned16(v);
   if (vec) attn_dbwd_rows_kernel<true><<<row_grid(rows), RB, 0, tg_stream(stream)>>>(s, lse, gp, u, v, rows, cols);
   else attn_dbwd_rows_kernel<false><<<row_grid(rows), RB, 0, tg_stream(stream)>>>(s, lse, gp, u, v, rows, cols);
+  return tg_launch_status();
+}
+
+int tg_filter_narrow(const float* bank, float* view, int O, int I, int Omax, int Imax, int taps, void* stream) {
+  TG_CHECK_PTR(bank); TG_CHECK_PTR(view);
+  TG_CHECK_POS(O); TG_CHECK_POS(I); TG_CHECK_POS(Omax); TG_CHECK_POS(Imax); TG_CHECK_POS(taps);
+  if (O > Omax || I > Imax) return TG_EINVAL;
+  const int64_t row = (int64_t)I * taps, total = row * O;
+  filter_narrow_kernel<<<tg_ew_grid(total, RB), RB, 0, tg_stream(stream)>>>(bank, view, total, row, (int64_t)Imax * taps);
+  return tg_launch_status();
+}
+
+int tg_filter_narrow_bwd(const float* gview, float* gbank, int O, int I, int Omax, int Imax, int taps, int accumulate, void* stream) {
+  TG_CHECK_PTR(gview); TG_CHECK_PTR(gbank);
+  TG_CHECK_POS(O); TG_CHECK_POS(I); TG_CHECK_POS(Omax); TG_CHECK_POS(Imax); TG_CHECK_POS(taps);
+  if (O > Omax || I > Imax) return TG_EINVAL;
+  const int64_t row = (int64_t)I * taps, bank_row = (int64_t)Imax * taps;
+  if (accumulate) {
+    const int64_t total = row * O;
+    filter_narrow_bwd_add_kernel<<<tg_ew_grid(total, RB), RB, 0, tg_stream(stream)>>>(gview, gbank, total, row, bank_row);
+  } else {
+    const int64_t total = bank_row * Omax;
+    filter_narrow_bwd_fill_kernel<<<tg_ew_grid(total, RB), RB, 0, tg_stream(stream)>>>(gview, gbank, total, O, row, bank_row);
+  }
   return tg_launch_status();
 }
 

@@ -1020,6 +1020,11 @@ def filter_forms(owner=None):
         _FilterForms.cache, _FilterForms.owner = outer, outer_owner
 
 
+def filter_forms_active():
+    """Is a ``filter_forms()`` scope open?"""
+    return _FilterForms.cache is not None
+
+
 _KNOWN_FORMS = weakref.WeakKeyDictionary()       # module -> {id(weight): weakref(weight)}; beside the module, not in it (pickling)
 
 
@@ -1077,6 +1082,80 @@ def _poolconv_weights(x_like, w):
         if _FilterForms.owner is not None and isinstance(w, torch.nn.Parameter):
             _known_forms(_FilterForms.owner)[id(w)] = weakref.ref(w)
     return w4, wp
+
+
+# =========================================================================== shared filter bank
+class _NarrowFilters(Function):
+    """bank [Omax, Imax, kh, kw] -> its dense [O, I, kh, kw] corner (reference models/shared/blocks.py:124-127:
+    ``filters.narrow(0, 0, out_dims).narrow(1, 0, in_dims)``), materialised because the convolution kernels take dense filters.
+    Linear: its backward is ``_NarrowFiltersT`` (the corner into a bank of zeros) and that one's backward is this one.  In a plain
+    backward inside ``grads_into_buckets()`` the corner is added straight into the bank's ``.grad`` (its FusedAdam bucket slot),
+    one launch per view in the order autograd reaches them: a fixed-order sum, bank elements no view covers stay exactly zero."""
+
+    @staticmethod
+    def forward(ctx, bank, O, I):
+        bank = bank.contiguous()
+        Omax, Imax = bank.shape[:2]
+        taps = bank[0, 0].numel()
+        view = bank.new_empty((O, I) + tuple(bank.shape[2:]))
+        K().filter_narrow(bank, view, O, I, Omax, Imax, taps)
+        ctx.bank_shape = tuple(bank.shape)
+        ctx.save_for_backward(bank)            # (for its .grad only: where the gradient goes in a plain backward)
+        return view
+
+    @staticmethod
+    def backward(ctx, gview):
+        if not (ctx.needs_input_grad[0] and _param_grads_wanted()):
+            return None, None, None
+        bank, = ctx.saved_tensors
+        sink = _grad_sink(bank)
+        if sink is not None and tuple(sink.shape) == ctx.bank_shape:
+            O, I = gview.shape[:2]
+            K().filter_narrow_bwd(gview.contiguous(), sink, O, I, ctx.bank_shape[0], ctx.bank_shape[1], gview[0, 0].numel(), 1)
+            return None, None, None
+        return _NarrowFiltersT.apply(gview, ctx.bank_shape[0], ctx.bank_shape[1]), None, None
+
+
+class _NarrowFiltersT(Function):
+    """transpose of ``_NarrowFilters``: [O, I, kh, kw] -> [Omax, Imax, kh, kw], exact zeros outside the corner"""
+
+    @staticmethod
+    def forward(ctx, gview, Omax, Imax):
+        gview = gview.contiguous()
+        O, I = gview.shape[:2]
+        gbank = gview.new_empty((Omax, Imax) + tuple(gview.shape[2:]))
+        K().filter_narrow_bwd(gview, gbank, O, I, Omax, Imax, gview[0, 0].numel(), 0)
+        ctx.corner = (O, I)
+        return gbank
+
+    @staticmethod
+    def backward(ctx, v):
+        return _NarrowFilters.apply(v, *ctx.corner), None, None
+
+
+def narrow_filters(bank, in_dims, out_dims):
+    """The first ``out_dims`` x ``in_dims`` filters of a shared bank as a dense filter tensor (the reference's
+    ``narrow_filters(filters, in_dims, out_dims)``, same argument order); twice differentiable.
+
+    Inside a ``filter_forms()`` scope -- the trainers bracket each pass over unchanged weights with one, and the shared models
+    open one around their own forward when none is active -- the view of a given (out, in) is materialised ONCE and every use
+    in the scope shares it (one copy forwards; autograd sums the uses' gradients, one launch into the bank backwards): a
+    4-block network has about five distinct shapes and a dozen uses.  Outside a scope every call materialises."""
+    O, I = int(out_dims), int(in_dims)
+    if bank.dim() < 3 or not (0 < O <= bank.shape[0] and 0 < I <= bank.shape[1]):
+        raise ValueError(f'narrow_filters: a ({O}, {I}) corner of a bank {tuple(bank.shape)}')
+    cache = _FilterForms.cache
+    if cache is None:
+        return _NarrowFilters.apply(bank, O, I)
+    # an entry keeps its bank alive (the address cannot be handed to another tensor inside the scope); a view made without a
+    # graph must not serve a pass that needs one
+    key = ('narrow', bank.data_ptr(), tuple(bank.shape), O, I, bank.requires_grad and torch.is_grad_enabled())
+    hit = cache.get(key)
+    if hit is not None and hit[0] is bank and hit[1] == bank._version:
+        return hit[2]
+    view = _NarrowFilters.apply(bank, O, I)
+    cache[key] = (bank, bank._version, view)
+    return view
 
 
 class _PoolConv(Function):
@@ -1671,6 +1750,95 @@ def bilinear_half(x):
 
 
 PAIR_SPECS[_BilinearHalf] = ('b', '', 'b')
+
+
+class _BilinearUp2x(Function):
+    """F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True) [+ residual]; linear, so its backward is the
+    transposed Function and that one's backward is this one."""
+
+    @staticmethod
+    def forward(ctx, x, residual=None):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        y = x.new_empty(B, C, 2 * H, 2 * W)
+        if residual is not None:
+            residual = residual.contiguous()
+            if residual.shape != y.shape:
+                raise RuntimeError(f'bilinear_up2x: residual {tuple(residual.shape)} for a result {tuple(y.shape)}')
+        K().bilinear_up2x_fwd(x, residual, y, B * C, H, W)
+        ctx.has_residual = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return _BilinearUp2xT.apply(g), (g if ctx.has_residual and ctx.needs_input_grad[1] else None)
+
+
+class _BilinearUp2xT(Function):
+    """transpose of the bilinear x2 map [+ residual]: (B, C, 2H, 2W) -> (B, C, H, W)"""
+
+    @staticmethod
+    def forward(ctx, gy, residual=None):
+        gy = gy.contiguous()
+        B, C, OH, OW = gy.shape
+        if OH % 2 or OW % 2:
+            raise RuntimeError('the transpose of bilinear_up2x needs even spatial dims')
+        gx = gy.new_empty(B, C, OH // 2, OW // 2)
+        if residual is not None:
+            residual = residual.contiguous()
+            if residual.shape != gx.shape:
+                raise RuntimeError(f'bilinear_up2x transpose: residual {tuple(residual.shape)} for a result {tuple(gx.shape)}')
+        K().bilinear_up2x_bwd(gy, residual, gx, B * C, OH // 2, OW // 2)
+        ctx.has_residual = residual is not None
+        return gx
+
+    @staticmethod
+    def backward(ctx, v):
+        return _BilinearUp2x.apply(v), (v if ctx.has_residual and ctx.needs_input_grad[1] else None)
+
+
+class _ForkBilinearUp2x(Function):
+    """x -> (up(x), up(x)) (one tensor, two graph edges): the shared generator block's upsampled input feeds the shortcut and
+    the main path; backward runs the transpose on both incoming gradients, the second adding onto the first at the LOW
+    resolution, instead of leaving a high-resolution add to the autograd engine."""
+    handles_none_grads = True
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        y = x.new_empty(B, C, 2 * H, 2 * W)
+        K().bilinear_up2x_fwd(x, None, y, B * C, H, W)
+        ctx.set_materialize_grads(False)
+        return y, y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        if ga is None or gb is None:
+            g = ga if gb is None else gb
+            return None if g is None else _BilinearUp2xT.apply(g)
+        return _BilinearUp2xT.apply(ga, _BilinearUp2xT.apply(gb))
+
+
+def bilinear_up2x(x, residual=None):
+    """F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True) [+ residual]; twice differentiable.  Per plane,
+    so a ``Pair`` is one launch over 2 B C planes."""
+    if _is_pair(x):
+        return pair_apply(_BilinearUp2x, x, residual)
+    return _BilinearUp2x.apply(x, residual)
+
+
+PAIR_SPECS[_BilinearUp2x] = ('bb', '', 'b')
+
+
+def fork_bilinear_up2x(x):
+    """-> (up, up) with up = bilinear_up2x(x), for two consumers"""
+    if _is_pair(x):
+        return pair_apply(_ForkBilinearUp2x, x)
+    return _ForkBilinearUp2x.apply(x)
+
+
+PAIR_SPECS[_ForkBilinearUp2x] = ('b', '', 'bb')
 
 
 class _MaxPool2(Function):

@@ -175,9 +175,11 @@ class Interpolate(nn.Module):
 
 
 def interpolate(x, size=None, scale_factor=None, mode='nearest', align_corners=None):
-    """F.interpolate for (scale 2, nearest) and (scale .5, bilinear, align_corners=True)."""
+    """F.interpolate for (scale 2, nearest), (scale .5, bilinear, align_corners=True) and (scale 2, bilinear, align_corners=True)."""
     if size is None and scale_factor == 2 and mode == 'nearest':
         return TF.upsample_nearest2x(x)
+    if size is None and scale_factor == 2 and mode == 'bilinear' and align_corners:
+        return TF.bilinear_up2x(x)
     if size is None and scale_factor == 0.5 and mode == 'bilinear' and align_corners:
         return TF.bilinear_half(x)
     raise NotImplementedError(f'interpolate(scale_factor={scale_factor}, mode={mode}, '
