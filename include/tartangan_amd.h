@@ -416,6 +416,17 @@ int tg_iqn_loss_groups(const float* preds, const float* target, const float* tau
  * nn.BCEWithLogitsLoss (mean) trainers/cnn.py:88,131,147; dlogits = (sigmoid(x)-t)/n    */
 int tg_bce_logits(const float* logits, const float* targets, float* loss, float* dlogits,
                   float* workspace, int n, void* stream);
+/* InfoGAN code loss (trainers/info.py:139-151, 167-180), forward and gradient in ONE launch.  codes: (B, C + K) dense logits;
+ * z: (B, ldz) latents, ldz >= C + K, whose first C + K columns are the targets, read in place.
+ *   cat  = mean over B*C of  max(x,0) - x*t + log1p(exp(-|x|))     (absent when C == 0)
+ *   cont = mean over B*K of  (x - t)^2                             (absent when K == 0)
+ *   out[0] = cat + cont;   out[1] = (base ? *base : 0) + w * out[0]
+ *   dcodes[b][c] = w (sigmoid(x) - t) / (B*C);   dcodes[b][C+k] = w 2 (x - t) / (B*K)
+ * One workgroup sums everything in a fixed order: no atomics, bit-identical between runs; `workspace` is not used (nullable;
+ * tg_reduce_workspace(B * (C + K)) is enough for any later version).  Every pointer may sit at any multiple of 4 bytes.
+ * B < 1, C < 0, K < 0, C + K == 0, ldz < C + K or a null codes / z / out / dcodes: TG_EINVAL, nothing written.                 */
+int tg_info_code_loss(const float* codes, const float* z, const float* base, float w, float* out, float* dcodes,
+                      float* workspace, int B, int C, int K, int ldz, void* stream);
 /* *out = alpha * sum x^2  (R1: grad.pow(2).view(B,-1).sum(1).mean(), losses.py:27-29)   */
 int tg_sumsq(const float* x, float alpha, float* out, float* workspace, int64_t n, void* stream);
 

@@ -220,6 +220,45 @@ __global__ void __launch_bounds__(RED_BLOCK) bce_stage1(const float* __restrict_
   if (threadIdx.x == 0) fin.put(partial, acc);
 }
 
+// InfoGAN code loss (trainers/info.py:139-151): BCE-with-logits over the C categorical columns plus MSE over the K continuous
+// ones, both means, against the first C + K columns of z (row stride ldz), and base + w * that.  ONE workgroup: the codes of a
+// batch are a few thousand elements at most, the cost is the launch, and a single block sums in a fixed order (no second stage,
+// no atomics).  Every access is a 4-byte one: the fake half of a paired head output starts at any row.
+constexpr int INFO_BLOCK = 1024;
+__global__ void __launch_bounds__(INFO_BLOCK) info_code_loss_kernel(const float* __restrict__ codes, const float* __restrict__ z,
+                                                                    const float* __restrict__ base, float w, float* __restrict__ out,
+                                                                    float* __restrict__ dcodes, int B, int C, int K, int ldz) {
+  __shared__ double scratch[32];
+  const int CK = C + K;
+  const int64_t n = (int64_t)B * CK;
+  const float wc = C ? w / (float)((int64_t)B * C) : 0.f, wk = K ? 2.f * w / (float)((int64_t)B * K) : 0.f;
+  double cat = 0.0, cont = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += INFO_BLOCK) {
+    const int64_t b = i / CK;
+    const int c = (int)(i - b * CK);
+    const float x = codes[i], t = z[b * ldz + c];
+    if (c < C) {
+      const float e = expf(-fabsf(x));
+      cat += (double)(fmaxf(x, 0.f) - x * t + log1pf(e));
+      // sigmoid(x) - t through s = sigmoid(-|x|) <= 1/2, which keeps its relative accuracy where sigmoid(x) is next to 1:
+      // (1 - t) is exact for the one-hot targets, so a saturated logit on its own target leaves -s, not a cancelled 1 - 1
+      const float sm = e / (1.f + e);
+      dcodes[i] = wc * (x >= 0.f ? (1.f - t) - sm : sm - t);
+    } else {
+      const float d = x - t;
+      cont += (double)d * (double)d;
+      dcodes[i] = wk * d;
+    }
+  }
+  cat = block_sum_d(cat, scratch);
+  cont = block_sum_d(cont, scratch);
+  if (threadIdx.x == 0) {
+    const float code = (float)((C ? cat / (double)((int64_t)B * C) : 0.0) + (K ? cont / (double)((int64_t)B * K) : 0.0));
+    out[0] = code;
+    out[1] = (base ? *base : 0.f) + w * code;
+  }
+}
+
 // IQN quantile Huber loss (models/iqn.py:111-130), out_dims = 1, row = q*B + b
 __global__ void __launch_bounds__(RED_BLOCK) iqn_loss_stage1(const float* __restrict__ preds, const float* __restrict__ target,
                                                              const float* __restrict__ taus, float k, float* __restrict__ dpreds,
@@ -349,6 +388,16 @@ int tg_bce_logits(const float* logits, const float* targets, float* loss, float*
   return tg_launch_status();
 }
 
+int tg_info_code_loss(const float* codes, const float* z, const float* base, float w, float* out, float* dcodes, float* workspace,
+                      int B, int C, int K, int ldz, void* stream) {
+  TG_CHECK_PTR(codes); TG_CHECK_PTR(z); TG_CHECK_PTR(out); TG_CHECK_PTR(dcodes);
+  TG_CHECK_POS(B);
+  if (C < 0 || K < 0 || C + K == 0 || ldz < C + K) return TG_EINVAL;
+  (void)workspace;        // one workgroup finishes the sum: no partials
+  info_code_loss_kernel<<<1, INFO_BLOCK, 0, tg_stream(stream)>>>(codes, z, base, w, out, dcodes, B, C, K, ldz);
+  return tg_launch_status();
+}
+
 int tg_iqn_loss_groups(const float* preds, const float* target, const float* taus, float k, float* loss, float* dpreds,
                        float* workspace, int Q, int B, int groups, void* stream) {
   TG_CHECK_PTR(preds); TG_CHECK_PTR(target); TG_CHECK_PTR(taus); TG_CHECK_PTR(loss); TG_CHECK_PTR(dpreds); TG_CHECK_PTR(workspace);
@@ -386,7 +435,7 @@ int tg_ema(float* t, const float* p, float lr, int64_t n, void* stream) {
   return tg_launch_status();
 }
 
-int tg_version(void) { return 102; }
+int tg_version(void) { return 103; }
 const char* tg_arch(void) { return "gfx950"; }
 
 }  // extern "C"

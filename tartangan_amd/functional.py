@@ -2727,6 +2727,42 @@ def bce_with_logits(logits, targets):
 PAIR_SPECS[_BCELogits] = ('b-', 'h', '-')
 
 
+class _InfoCodeLoss(Function):
+    """InfoGAN code loss and ``base + w * code loss`` from one launch (tg_info_code_loss); the targets are read out of ``z`` in
+    place.  The first output is the reported, unweighted value: no graph.  A missing gradient stays missing."""
+    handles_none_grads = True
+
+    @staticmethod
+    def forward(ctx, p_codes, z, base, cat_dims, cont_dims, w):
+        pc, z = p_codes.contiguous(), z.contiguous()
+        if base is not None:
+            base = base.contiguous()
+        out = pc.new_empty(2)
+        dcodes = torch.empty_like(pc)
+        K().info_code_loss(pc, z, base, w, out, dcodes, None, pc.shape[0], cat_dims, cont_dims, z.shape[1])
+        _ScaledGrad._finish(ctx, p_codes, dcodes)
+        code, total = out[0], out[1]
+        ctx.mark_non_differentiable(code)
+        return code, total
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _, g):
+        gc = _ScaledGrad._bwd(ctx, g) if ctx.needs_input_grad[0] else None
+        return gc, None, (g if ctx.needs_input_grad[2] else None), None, None, None
+
+
+def info_code_loss(p_codes, z, cat_dims, cont_dims, w, base=None):
+    """trainers/info.py:139-151: BCE-with-logits of ``p_codes[:, :C]`` against ``z[:, :C]`` plus MSE of ``p_codes[:, C:C+K]``
+    against ``z[:, C:C+K]`` -> (code_loss, total): ``code_loss`` the unweighted sum of the two means (reported, not
+    differentiable), ``total = base + w * code_loss`` (``base``: a 0-d loss, or None for zero) with the graph -- ``g * dcodes``
+    to ``p_codes``, ``g`` to ``base``, nothing to ``z``."""
+    cat_dims, cont_dims = int(cat_dims), int(cont_dims)
+    if p_codes.dim() != 2 or z.dim() != 2 or p_codes.shape[1] != cat_dims + cont_dims or z.shape[0] != p_codes.shape[0]:
+        raise ValueError(f'info_code_loss: codes {tuple(p_codes.shape)} / z {tuple(z.shape)} do not fit C = {cat_dims}, K = {cont_dims}')
+    return _InfoCodeLoss.apply(p_codes, z, base, cat_dims, cont_dims, float(w))
+
+
 class _SumSq(Function):
     @staticmethod
     def forward(ctx, x, alpha):

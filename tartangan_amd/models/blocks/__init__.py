@@ -1,6 +1,7 @@
 from .attention import SelfAttention2d  # noqa
 from .discriminator import (  # noqa
-    DiscriminatorInput, DiscriminatorOutput, IQNDiscriminatorOutput, ResidualDiscriminatorBlock,
+    DiscriminatorInput, DiscriminatorOutput, IQNDiscriminatorOutput, LinearOutput, MultiModelDiscriminatorOutput,
+    ResidualDiscriminatorBlock,
 )
 from .generator import (  # noqa
     GeneratorInputMLP, GeneratorOutput, ResidualGeneratorBlock, TiledZGeneratorInput,

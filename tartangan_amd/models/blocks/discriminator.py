@@ -2,7 +2,8 @@
 
 Implemented: ``DiscriminatorInput`` (discriminator.py:11-22),
 ``ResidualDiscriminatorBlock`` (:49-95), ``DiscriminatorOutput`` (:126-146),
-``IQNDiscriminatorOutput`` (:149-178).  Every op here is differentiable twice
+``IQNDiscriminatorOutput`` (:149-178), ``MultiModelDiscriminatorOutput`` (:181-201),
+``LinearOutput`` (:204-213).  Every op here is differentiable twice
 (the real-image branch sits under the R1 penalty).
 """
 import functools
@@ -111,6 +112,46 @@ class DiscriminatorOutput(nn.Module):
     def forward(self, feats):
         feats = TF.sum_hw(run_layers(self.activation, feats))
         return run_layers(self.to_output, feats)
+
+
+class LinearOutput(nn.Module):
+    """Linear -> activation: one head of ``MultiModelDiscriminatorOutput``."""
+
+    def __init__(self, in_dims, out_dims, activation_factory=nn.Identity):
+        super().__init__()
+        self.xform = nn.Sequential(Linear(in_dims, out_dims), activation_factory())
+        self.out_dims = out_dims
+
+    def forward(self, x):
+        if self.out_dims == 0:           # (InfoGAN without codes: a head of no columns has nothing to launch)
+            if isinstance(x, TF.Pair):
+                return TF.Pair(x.r.new_empty(x.r.shape[0], 0), x.f.new_empty(x.f.shape[0], 0))
+            return x.new_empty(x.shape[0], 0)
+        return run_layers(self.xform, x)
+
+
+class MultiModelDiscriminatorOutput(nn.Module):
+    """norm -> act -> sum over (H, W) -> [head(feats) for head in output_models]: a list, one entry per head.  A ``Pair`` goes
+    in, a list of Pairs comes out."""
+
+    def __init__(self, in_dims, out_dims, output_model_factories, norm_factory=BatchNorm2d, activation_factory=_lrelu):
+        super().__init__()
+        self.activation = nn.Sequential(norm_factory(in_dims), activation_factory())
+        self.output_models = nn.ModuleList([factory(in_dims) for factory in output_model_factories])
+
+    def forward(self, feats):
+        feats = TF.sum_hw(run_layers(self.activation, feats))
+        n = len(self.output_models)
+        if not 2 <= n <= 4:
+            return [model(feats) for model in self.output_models]
+        # The heads' gradients meet at ``feats``: one fan-in kernel instead of the autograd engine's adds.  The halves of a Pair
+        # fork separately, so a half that only some heads are differentiated through (the real half's codes are discarded,
+        # trainers/info.py:135) sums the gradients that arrive and nobody makes up a zero one for the rest.
+        if isinstance(feats, TF.Pair):
+            copies = [TF.Pair(r, f) for r, f in zip(TF.fork(feats.r, n), TF.fork(feats.f, n))]
+        else:
+            copies = TF.fork(feats, n)
+        return [model(x) for model, x in zip(self.output_models, copies)]
 
 
 class IQNDiscriminatorOutput(nn.Module):

@@ -131,7 +131,7 @@ class CNNTrainer(Trainer):
         toggle_grad(self.d, True)
         self.optimizer_d.zero_grad()
         if both_fakes is None:
-            fake = self.sample_g(bs)
+            fake = self._sample_fake(bs)
         else:
             fake, self._fake_for_g_phase = both_fakes
         labels = self._labels(bs)
@@ -179,7 +179,15 @@ class CNNTrainer(Trainer):
         if fake is not None:
             self.sample_z(bs)          # this phase's latent in the step's RNG plan: the paired forward of the D phase used it
             return fake
+        return self._sample_fake(bs)
+
+    def _sample_fake(self, bs):
+        """A phase's generated batch (a subclass whose ``sample_g`` returns more than the images takes them out here)."""
         return self.sample_g(bs)
+
+    def _latent_entry(self, bs):
+        """The plan entry of one phase's latents."""
+        return ('z', bs, self.gan_config.latent_dims)
 
     def _generator_forward_for_both_phases(self, bs):
         """The generator runs twice per step with the SAME weights -- ``sample_g`` of the D phase (cnn.py:117, no gradient)
@@ -191,8 +199,9 @@ class CNNTrainer(Trainer):
         if not (self._in_step and feed.mode == 'serve' and self._g_pairable()):
             return None
         i = feed.cursor
-        later = [k for k in range(i + 1, len(feed.plan)) if feed.plan[k][0] == 'z']
-        if i >= len(feed.plan) or feed.plan[i] != ('z', bs, self.gan_config.latent_dims) or not later or feed.plan[later[0]] != feed.plan[i]:
+        entry = self._latent_entry(bs)
+        later = [k for k in range(i + 1, len(feed.plan)) if feed.plan[k][0] == entry[0]]
+        if i >= len(feed.plan) or feed.plan[i] != entry or not later or feed.plan[later[0]] != feed.plan[i]:
             return None
         z_d = self.sample_z(bs)
         z_g = feed.static[later[0]]              # (its plan entry is consumed by the G phase, see _g_forward)
@@ -202,7 +211,7 @@ class CNNTrainer(Trainer):
 
     def _rng_plan(self, bs):
         """Random inputs of one step in draw order: the D phase's latents, the G phase's latents (trainer.py:153-156)."""
-        z = ('z', bs, self.gan_config.latent_dims)
+        z = self._latent_entry(bs)
         return [z, z]
 
     def _known_rng_plan(self, bs):
@@ -282,7 +291,13 @@ class CNNTrainer(Trainer):
             vals = torch.stack([v for v in vals if v is not None])
         if feed.mode == 'serve' and restore is None and getattr(self.args, 'prefetch_rng', _PREFETCH_RNG):
             feed.prefetch()          # the next step's latents, drawn under this step's GPU time (see RngFeed.prefetch)
-        vals = self._read_back(vals)                                         # one device->host read
+        return self._logs(self._read_back(vals))                             # one device->host read
+
+    def _step_losses(self, g_loss, d_loss, d_grad_penalty):
+        """The step's device scalars in read-back order (None: absent from the read-back)."""
+        return g_loss, d_loss, d_grad_penalty
+
+    def _logs(self, vals):
         return dict(g_loss=vals[0], d_loss=vals[1], gp=vals[2] if len(vals) > 2 else 0.)
 
     def _read_back(self, vals):
@@ -320,7 +335,7 @@ class CNNTrainer(Trainer):
         self._finish_reduce('g')
         self.optimizer_g.step()
         self.update_target_generator()
-        return g_loss, d_loss, d_grad_penalty
+        return self._step_losses(g_loss, d_loss, d_grad_penalty)
 
     # ------------------------------------------------------------------ HIP-graph replay of the step
     def enable_graphs(self):
@@ -396,7 +411,7 @@ class CNNTrainer(Trainer):
             self.optimizer_g.apply()
             self.update_target_generator()
             # the losses side by side in one static buffer: the replayed step reads back ONE tensor, no launch of its own
-            self._out_losses = torch.stack([v for v in (self._out_g, self._out_d[0], self._out_d[1]) if v is not None])
+            self._out_losses = torch.stack([v for v in self._step_losses(self._out_g, *self._out_d) if v is not None])
         self._buckets_in_graph = inside
         self._graphs = (g1, g2a, g2b, g3)
         feed.cursor = 0

@@ -10,9 +10,21 @@ is the drop-in boundary.
 """
 import argparse
 
+import numpy as np
 import torch
 
 from .utils import set_device_from_args
+
+
+def write_codes(z, cat_dims, cats):
+    """The categorical code of InfoGAN latents (trainers/info.py:209-212): columns [0, cat_dims) zeroed, a one at ``cats[row]``."""
+    z[:, :cat_dims] = 0.
+    z[torch.arange(z.shape[0]), torch.as_tensor(cats, dtype=torch.long)] = 1.
+    return z
+
+
+def _same_numpy_state(a, b):
+    return a[0] == b[0] and np.array_equal(a[1], b[1]) and tuple(a[2:]) == tuple(b[2:])
 
 
 class RngFeed:
@@ -25,7 +37,10 @@ class RngFeed:
     afterwards ``refill`` reproduces it.  Under data parallelism every rank draws the GLOBAL
     tensor from the same seed and keeps its own rows (tau rows are quantile-major:
     row = q * B + b), so the union over ranks is the single-process stream.  Kind 'noise' is one (rows, cols) normal draw
-    shared by the whole batch (models/blocks/scene.py:139-140): identical on every rank, never sliced.
+    shared by the whole batch (models/blocks/scene.py:139-140): identical on every rank, never sliced.  Kind 'zc' is a latent
+    that carries InfoGAN's categorical code in its first ``cat_dims`` columns (trainers/info.py:204-213): a 'z' draw, then one
+    ``np.random.randint(0, cat_dims, rows)`` from numpy's GLOBAL generator -- a second host stream -- written as a one-hot row
+    by row.  The code is composed on the host, in the staging buffer, so the static device buffer holds the finished latent.
     """
 
     def __init__(self, device, rank=0, world=1):
@@ -36,13 +51,18 @@ class RngFeed:
         self.mode = 'record'
         self.cursor = 0
         self.key = None         # batch shape the plan was recorded for
-        self._spec = None       # (generator state before, after) a speculative draw of the next step's inputs
+        self.cat_dims = 0       # width of the categorical code of kind 'zc'
+        self._spec = None       # (host generator states before, after) a speculative draw of the next step's inputs
         self._uploaded = None   # event behind the last host -> device copies of the staging buffers
         self._arena = self._host_arena = None   # one allocation behind all of an adopted plan's buffers
 
     def _draw_cpu(self, kind, rows, cols):
         if kind == 'z':
             full = torch.randn(rows * self.world, cols)
+            return full[self.rank * rows:(self.rank + 1) * rows]
+        if kind == 'zc':
+            full = write_codes(torch.randn(rows * self.world, cols), self.cat_dims,
+                               np.random.randint(0, self.cat_dims, rows * self.world))
             return full[self.rank * rows:(self.rank + 1) * rows]
         if kind == 'noise':
             return torch.randn(rows, cols)
@@ -54,7 +74,7 @@ class RngFeed:
 
     def draw(self, kind, rows, cols):
         """kind 'z': (rows, cols) normal;  kind 'tau': (rows, 1) uniform with cols = num_quantiles;  kind 'noise': (rows, cols)
-        normal, the same on every rank."""
+        normal, the same on every rank;  kind 'zc': 'z' with the one-hot categorical code in its first ``cat_dims`` columns."""
         if self.mode == 'off':
             return self._draw_cpu(kind, rows, cols).contiguous().to(self.device)
         if self.mode == 'record':
@@ -79,7 +99,7 @@ class RngFeed:
         generator passes of a step run over them as one (2B, latent) tensor without joining them first (functional._join)."""
         self.plan = [tuple(p) for p in plan]
         sizes = [rows * (1 if kind == 'tau' else cols) for kind, rows, cols in self.plan]
-        order = sorted(range(len(self.plan)), key=lambda i: (self.plan[i][0] != 'z', i))
+        order = sorted(range(len(self.plan)), key=lambda i: (self.plan[i][0] not in ('z', 'zc'), i))
         offsets, total = {}, 0
         for i in order:
             offsets[i] = total
@@ -100,6 +120,8 @@ class RngFeed:
                 # straight into the pinned staging buffer: ``torch.randn(r, c)`` is ``empty(r, c).normal_()`` and
                 # ``torch.rand(r, 1)`` is ``empty(r, 1).uniform_()`` -- the same values from the same generator state
                 host.uniform_() if kind == 'tau' else host.normal_()
+                if kind == 'zc':
+                    write_codes(host, self.cat_dims, np.random.randint(0, self.cat_dims, rows))
             else:
                 host.copy_(self._draw_cpu(kind, rows, cols))
 
@@ -117,16 +139,31 @@ class RngFeed:
             return
         if self._uploaded is not None:
             self._uploaded.synchronize()          # the staging buffers are free (the copies ran at the head of this step)
-        before = torch.get_rng_state()
+        before = self._host_streams()
         self._draw_into_host()
-        after = torch.get_rng_state()
-        torch.set_rng_state(before)
+        after = self._host_streams()
+        self._restore_host_streams(before)
         self._spec = (before, after)
+
+    def _host_streams(self):
+        """State of every host generator the plan draws from: torch's, and numpy's global one when a 'zc' entry reads it."""
+        uses_numpy = any(kind == 'zc' for kind, _, _ in self.plan)
+        return torch.get_rng_state(), (np.random.get_state() if uses_numpy else None)
+
+    @staticmethod
+    def _restore_host_streams(state):
+        torch.set_rng_state(state[0])
+        if state[1] is not None:
+            np.random.set_state(state[1])
+
+    def _streams_are_at(self, state):
+        now = self._host_streams()
+        return torch.equal(now[0], state[0]) and (state[1] is None or _same_numpy_state(now[1], state[1]))
 
     def refill(self):
         spec, self._spec = self._spec, None
-        if spec is not None and torch.equal(torch.get_rng_state(), spec[0]):
-            torch.set_rng_state(spec[1])
+        if spec is not None and self._streams_are_at(spec[0]):       # BOTH streams where the speculation left them
+            self._restore_host_streams(spec[1])
         else:
             if self._uploaded is not None:
                 self._uploaded.synchronize()
