@@ -411,6 +411,40 @@ int tg_iqn_loss(const float* preds, const float* target, const float* taus, floa
  * (trainers/iqn.py:118-120: loss_real + loss_fake), dpreds per evaluation as above */
 int tg_iqn_loss_groups(const float* preds, const float* target, const float* taus, float k,
                        float* loss, float* dpreds, float* workspace, int Q, int B, int groups, void* stream);
+/* The head of IQNDiscriminatorOutput behind the pooled features (discriminator.py:149-178 after sum(x, [2, 3]); iqn.py:27-46,
+ * 76-108 with mix = 'mult', 111-130), fused: cosine embedding -> Linear(D, C) -> tanh -> * features -> Linear(C, 1) -> quantile
+ * mean and quantile Huber loss.  f (G*B, C): the pooled features of G in {1, 2} evaluations back to back; taus (G*Q*B), row
+ * r = g*Q*B + q*B + b; target (G*B); W1 (C, D), b1 (C); w2 (C), b2 (1, nullable = 0); range (D).
+ *   e[r][j] = cos((taus[r] * pi) * range[j])                     (tg_iqn_cos_embed's evaluation order)
+ *   s[r][c] = tanh(b1[c] + sum_j e[r][j] W1[c][j])
+ *   p[r]    = b2 + sum_c f[g*B + b][c] * s[r][c] * w2[c]
+ *   pt[g*B + b] = (1/Q) sum_q p[r]
+ *   *loss   = sum_g (1/B) sum_q,b |tau - 1[err<0]| * huber_k(err),  err = target - p   (the SUM over g, as tg_iqn_loss_groups)
+ *   dpreds[r] = d loss / d p[r]
+ * tg_iqn_head_fwd writes pt, and *loss and dpreds when `target` is given (then `loss`, `dpreds` and `workspace` of
+ * tg_iqn_head_workspace(G, B) bytes are required; without `target` none of the three is touched).  Neither s nor the repeated
+ * features are stored: tg_iqn_head_bwd recomputes s.  One workgroup per (g, b) sums its rows in a fixed order, a one-workgroup
+ * second launch sums the G*B loss terms (none when G*B == 1; they cross in `workspace` as pairs of 32-bit words): no atomics,
+ * bit-identical between runs.
+ *
+ * tg_iqn_head_bwd: the cotangent of the rows is delta[r] = gl[0] * dpreds[r] + gpt[g*B + b] / Q, each part nullable (`dpreds` is
+ * required with `gl`).  Outputs, each nullable:
+ *   df[g*B + b][c] = w2[c] * sum_q delta[r] s[r][c]
+ *   dw2[c]   = sum_r delta[r] f[..][c] s[r][c]         db2[0]  = sum_r delta[r]
+ *   da[r][c] = delta[r] f[..][c] w2[c] (1 - s[r][c]^2) dW1[c][j] = sum_r da[r][c] e[r][j]      db1[c] = sum_r da[r][c]
+ * accumulate != 0: dW1, db1, dw2 and db2 are added to (df is always overwritten).  Every output is complete inside one
+ * workgroup (a slab of channels walking all rows in a fixed order): no atomics, bit-identical between runs.
+ * Every pointer may sit at any multiple of 4 bytes.  A null required pointer, G outside {1, 2}, B, Q, C or D < 1: TG_EINVAL;
+ * D > 20: TG_EUNSUPPORTED; nothing launched or written.                                                                          */
+size_t tg_iqn_head_workspace(int G, int B);
+int tg_iqn_head_fwd(const float* f, const float* taus, const float* target /*nullable*/, const float* W1, const float* b1,
+                    const float* w2, const float* b2 /*nullable*/, const float* range, float k, float* pt,
+                    float* loss /*nullable*/, float* dpreds /*nullable*/, float* workspace /*nullable*/,
+                    int G, int B, int Q, int C, int D, void* stream);
+int tg_iqn_head_bwd(const float* gl /*nullable*/, const float* gpt /*nullable*/, const float* dpreds /*nullable*/,
+                    const float* f, const float* taus, const float* W1, const float* b1, const float* w2, const float* range,
+                    float* df /*nullable*/, float* dW1 /*nullable*/, float* db1 /*nullable*/, float* dw2 /*nullable*/,
+                    float* db2 /*nullable*/, int G, int B, int Q, int C, int D, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------- losses
  * nn.BCEWithLogitsLoss (mean) trainers/cnn.py:88,131,147; dlogits = (sigmoid(x)-t)/n    */

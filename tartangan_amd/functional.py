@@ -2699,6 +2699,170 @@ def iqn_quantile_huber_loss(preds, target, taus, num_quantiles, k=1.0):
     return _IQNLoss.apply(preds, target, taus, num_quantiles, k)
 
 
+# ---- the fused head (tg_iqn_head_fwd / tg_iqn_head_bwd)
+def _iqn_head_param_grads(gl, gpt, dpreds, f, taus, params, rng, dims, df=None, need=(True, True, True, True), sinks_ok=True):
+    """One tg_iqn_head_bwd launch: the gradients of (W1, b1, w2, b2) that ``need`` asks for (and ``df``, when a buffer is
+    given).  A parameter that owns a slot in a gradient bucket gets its gradient added there (-> None for it, see
+    ``_grad_sink``); the others come back as tensors."""
+    W1, b1, w2, b2 = params
+    G, B, Q, C, D = dims
+    ps = [p if n else None for p, n in zip(params, need)]
+    sinks = [None if (p is None or not sinks_ok) else _grad_sink(p) for p in ps]
+    wanted = [p for p in ps if p is not None]
+    direct = bool(wanted) and all(s is not None for p, s in zip(ps, sinks) if p is not None)
+    if direct:
+        outs, res = sinks, [None] * 4
+    else:
+        outs = [None if p is None else torch.empty_like(p, memory_format=torch.contiguous_format) for p in ps]
+        res = outs
+    if df is not None or wanted:
+        K().iqn_head_bwd(gl, gpt, dpreds, f, taus, W1, b1, w2, rng, df, outs[0], outs[1], outs[2], outs[3],
+                         G, B, Q, C, D, int(direct))
+    return tuple(res)
+
+
+class _IQNHeadBwd(Function):
+    """tg_iqn_head_bwd as a graph node: (gl, gpt) -> (df, dW1, db1, dw2, db2).  Its own backward (the R1 penalty's sweep arrives
+    with a cotangent ``v`` on ``df``) needs no third kernel: <v, df> = psi(v, delta), so the gradient w.r.t. ``gpt`` is the
+    forward kernel's ``pt`` on ``f := v`` without ``b2``, the gradients w.r.t. W1, b1, w2 are this kernel's on ``f := v`` with the
+    same delta, and ``df`` does not depend on ``f``.  ``dpreds`` is a constant of the second order, as with ``_IQNLoss``."""
+    handles_none_grads = True
+
+    @staticmethod
+    def forward(ctx, gl, gpt, dpreds, f, taus, W1, b1, w2, b2, rng, dims, want_df, want_params, sinks_ok):
+        G, B, Q, C, D = dims
+        gl = None if gl is None else gl.contiguous()
+        gpt = None if gpt is None else gpt.contiguous()
+        f = f.contiguous()
+        df = f.new_empty(G * B, C) if want_df else None
+        need = tuple(bool(want_params and p is not None and p.requires_grad) for p in (W1, b1, w2, b2))
+        grads = _iqn_head_param_grads(gl, gpt, dpreds, f, taus, (W1, b1, w2, b2), rng, dims, df=df, need=need, sinks_ok=sinks_ok)
+        ctx.save_for_backward(gl, gpt, dpreds, taus, W1, b1, w2, rng)
+        ctx.dims = dims
+        return (df,) + grads
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, v, *param_cotangents):
+        if any(g is not None for g in param_cotangents):
+            raise NotImplementedError('iqn_head: a gradient THROUGH the head\'s parameter gradients (dW1, db1, dw2, db2) is not '
+                                      'implemented; only df is differentiable a second time')
+        gl, gpt, dpreds, taus, W1, b1, w2, rng = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if need[0]:
+            raise NotImplementedError('iqn_head: the second-order gradient w.r.t. the cotangent of the loss is not implemented '
+                                      '(the loss is differentiable once, like iqn_quantile_huber_loss)')
+        G, B, Q, C, D = ctx.dims
+        v = v.contiguous()
+        g_gpt = None
+        if need[1]:
+            g_gpt = v.new_empty(gpt.shape)
+            K().iqn_head_fwd(v, taus, None, W1, b1, w2, None, rng, 1.0, g_gpt, None, None, None, G, B, Q, C, D)
+        gW1 = gb1 = gw2 = None
+        if (need[5] or need[6] or need[7]) and _param_grads_wanted():
+            gW1, gb1, gw2, _ = _iqn_head_param_grads(gl, gpt, dpreds, v, taus, (W1, b1, w2, None), rng, ctx.dims,
+                                                     need=(need[5], need[6], need[7], False))
+        return None, g_gpt, None, None, None, gW1, gb1, gw2, None, None, None, None, None, None
+
+
+class _IQNHead(Function):
+    """The head of ``IQNDiscriminatorOutput`` behind the pooled features in one launch (plus the loss's finisher):
+    (f_r, f_f | None, taus, targets | None, W1, b1, w2, b2, range) -> (pt_r, pt_f | None, loss | None).  With ``f_f`` the two
+    evaluations of a D phase run back to back (G = 2; ``taus`` and ``targets`` hold both, real first) and the loss is their sum.
+    The backward is ``_IQNHeadBwd``: a cotangent on one half's ``pt`` alone (the R1 penalty's first-order pass) runs on that half
+    as G = 1, exactly the graph the unpaired pass would build."""
+    handles_none_grads = True
+
+    @staticmethod
+    def forward(ctx, f_r, f_f, taus, targets, W1, b1, w2, b2, rng, Q, k):
+        G = 1 if f_f is None else 2
+        f = f_r.contiguous() if G == 1 else _join(f_r.contiguous(), f_f.contiguous())
+        B, C = f_r.shape
+        D = rng.shape[0]
+        taus = taus.contiguous()             # (the parameters are handed on as they are: the backward looks for their buckets)
+        pt = f.new_empty(G * B, 1)
+        loss = dpreds = ws = None
+        if targets is not None:
+            targets = targets.contiguous()
+            loss, dpreds = f.new_empty(()), f.new_empty(G * Q * B)
+            ws = _ws(f, K().iqn_head_workspace(G, B))
+        K().iqn_head_fwd(f, taus, targets, W1, b1, w2, b2, rng, float(k), pt, loss, dpreds, ws, G, B, Q, C, D)
+        ctx.save_for_backward(f_r, f_f, taus, dpreds, W1, b1, w2, b2, rng)
+        ctx.dims = (G, B, Q, C, D)
+        ctx.set_materialize_grads(False)
+        if G == 1:
+            return pt, None, loss
+        return pt[:B], pt[B:], loss
+
+    @staticmethod
+    def backward(ctx, g_r, g_f, g_loss):
+        f_r, f_f, taus, dpreds, W1, b1, w2, b2, rng = ctx.saved_tensors
+        G, B, Q, C, D = ctx.dims
+        need = ctx.needs_input_grad
+        want_params = _param_grads_wanted() and any(need[4:8])
+        sinks_ok = not torch.is_grad_enabled()         # (create_graph: the parameter gradients belong to the new graph)
+        none = (None,) * 11
+        if G == 2 and g_loss is None and (g_r is None) != (g_f is None):
+            # one half alone: that half's rows as an evaluation of its own
+            real = g_f is None
+            fh = f_r if real else f_f
+            n = Q * B
+            if not (need[0 if real else 1] or want_params):
+                return none
+            out = _IQNHeadBwd.apply(None, g_r if real else g_f, None, fh, taus[:n] if real else taus[n:], W1, b1, w2, b2, rng,
+                                    (1, B, Q, C, D), need[0 if real else 1], want_params, sinks_ok)
+            df = out[0]
+            return ((df, None) if real else (None, df)) + (None, None) + tuple(out[1:5]) + (None, None, None)
+        gpt = None
+        if G == 1:
+            gpt = g_r
+        elif g_r is not None or g_f is not None:
+            zeros = lambda: torch.zeros(B, 1, dtype=f_r.dtype, device=f_r.device)
+            gpt = _join((g_r if g_r is not None else zeros()).contiguous(), (g_f if g_f is not None else zeros()).contiguous())
+        want_df = need[0] or (G == 2 and need[1])
+        if not (want_df or want_params):
+            return none
+        f = f_r if G == 1 else _join(f_r.contiguous(), f_f.contiguous())
+        out = _IQNHeadBwd.apply(g_loss, gpt, dpreds if g_loss is not None else None, f, taus, W1, b1, w2, b2, rng, ctx.dims,
+                                want_df, want_params, sinks_ok)
+        df = out[0]
+        if df is None:
+            dfs = (None, None)
+        elif G == 1:
+            dfs = (df, None)
+        else:
+            dfs = (df[:B] if need[0] else None, df[B:] if need[1] else None)
+        return dfs + (None, None) + tuple(out[1:5]) + (None, None, None)
+
+
+def iqn_head(feats, taus, targets, W1, b1, w2, b2, embedding_range, num_quantiles, k=1.0):
+    """The IQN head behind the pooled features, fused: ``feats`` (B, C) and ``taus`` (Q*B, 1) with row = q*B + b ->
+    (p_target (B, 1), loss | None), where p = Linear(w2, b2)(feats.repeat(Q, 1) * tanh(Linear(W1, b1)(cos(pi tau range)))),
+    p_target its mean over the quantiles and loss the quantile Huber loss against ``targets`` (B, 1) (None: no loss).  ``feats``
+    and ``taus`` Pairs (``targets`` (2B, 1), real first): both evaluations in one launch, p_target a Pair, loss the sum of the two.
+    Differentiable twice through p_target w.r.t. feats, W1, b1, w2 (the R1 penalty); the loss once."""
+    Q = int(num_quantiles)
+    n_images = len(feats)
+    if targets is not None and (targets.requires_grad or targets.numel() != n_images):
+        raise ValueError(f'iqn_head: targets {tuple(targets.shape)} must be one constant per image ({n_images})')
+    def check(f, t):
+        if (f.dim() != 2 or t.numel() != Q * f.shape[0] or tuple(W1.shape) != (f.shape[1], embedding_range.shape[0])
+                or b1.numel() != f.shape[1] or w2.numel() != f.shape[1] or b2.numel() != 1):
+            raise ValueError(f'iqn_head: feats {tuple(f.shape)}, taus {tuple(t.shape)}, W1 {tuple(W1.shape)}, b1 {tuple(b1.shape)}, '
+                             f'w2 {tuple(w2.shape)}, b2 {tuple(b2.shape)} do not fit Q = {Q}, D = {embedding_range.shape[0]}')
+    if _is_pair(feats):
+        if not _is_pair(taus):
+            raise TypeError('iqn_head: a Pair of features needs a Pair of taus')
+        check(feats.r, taus.r)
+        check(feats.f, taus.f)
+        both = _join(taus.r.contiguous().view(-1), taus.f.contiguous().view(-1))
+        pt_r, pt_f, loss = _IQNHead.apply(feats.r, feats.f, both, targets, W1, b1, w2, b2, embedding_range, Q, float(k))
+        return Pair(pt_r, pt_f), loss
+    check(feats, taus)
+    pt, _, loss = _IQNHead.apply(feats, None, taus.view(-1), targets, W1, b1, w2, b2, embedding_range, Q, float(k))
+    return pt, loss
+
+
 class _BCELogits(Function):
     @staticmethod
     def forward(ctx, logits, targets):

@@ -1,6 +1,6 @@
 from .attention import SelfAttention2d  # noqa
 from .discriminator import (  # noqa
-    DiscriminatorInput, DiscriminatorOutput, IQNDiscriminatorOutput, LinearOutput, MultiModelDiscriminatorOutput,
+    DiscriminatorInput, DiscriminatorOutput, FusedIQNDiscriminatorOutput, IQNDiscriminatorOutput, LinearOutput, MultiModelDiscriminatorOutput,
     ResidualDiscriminatorBlock,
 )
 from .generator import (  # noqa

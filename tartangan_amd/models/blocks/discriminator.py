@@ -2,18 +2,20 @@
 
 Implemented: ``DiscriminatorInput`` (discriminator.py:11-22),
 ``ResidualDiscriminatorBlock`` (:49-95), ``DiscriminatorOutput`` (:126-146),
-``IQNDiscriminatorOutput`` (:149-178), ``MultiModelDiscriminatorOutput`` (:181-201),
+``IQNDiscriminatorOutput`` (:149-178; ``FusedIQNDiscriminatorOutput``: the same head on one kernel each way),
+``MultiModelDiscriminatorOutput`` (:181-201),
 ``LinearOutput`` (:204-213).  Every op here is differentiable twice
 (the real-image branch sits under the R1 penalty).
 """
 import functools
+import os
 
 import torch
 from torch import nn
 
 from ... import functional as TF
-from ..iqn import IQN, iqn_loss
-from ..layers import AvgPool2d, BatchNorm2d, Conv2d, LeakyReLU, Linear, interpolate, run_layers
+from ..iqn import IQN, CosineQuantileEmbedding, iqn_loss
+from ..layers import AvgPool2d, BatchNorm2d, Conv2d, LeakyReLU, Linear, Tanh, interpolate, run_layers
 
 _lrelu = functools.partial(LeakyReLU, 0.2)
 _half = functools.partial(interpolate, scale_factor=0.5, mode='bilinear', align_corners=True)
@@ -175,6 +177,41 @@ class IQNDiscriminatorOutput(nn.Module):
                 raise NotImplementedError('IQN loss kernel covers out_dims == 1 (the trainers\' case)')
             loss = iqn_loss(p_target_tau, targets, taus)
         p_target = TF.mean_reps(p_target_tau, self.iqn.num_quantiles)
+        if targets is not None:
+            return p_target, loss
+        return p_target
+
+
+class FusedIQNDiscriminatorOutput(IQNDiscriminatorOutput):
+    """``IQNDiscriminatorOutput`` whose part behind the pooled features -- embedding, mix, Linear, quantile mean, loss -- is one
+    launch each way (``functional.iqn_head``) instead of ~35.  Same constructor, submodules and ``state_dict`` keys; the taus are
+    drawn exactly as the composed head draws them (real first, then fake, for a Pair).  BatchNorm -> activation -> sum pool stay
+    on their own kernels.  The composed forward of the parent runs instead when the head is not the one the kernel implements
+    (``iqn.mix`` other than 'mult', another quantile embedding or activation than cosine + Tanh, more than 20 embedding dims,
+    ``out_dims != 1``) or when ``TG_IQN_FUSED_HEAD=0`` is in the environment (read at every call)."""
+
+    def fused(self):
+        emb = self.iqn.quantile_embedding
+        if os.environ.get('TG_IQN_FUSED_HEAD', '1') == '0' or self.iqn.mix != 'mult' or self.out_dims != 1:
+            return False
+        if type(emb) is not CosineQuantileEmbedding or len(emb.to_state) != 2 or len(self.to_output) != 1:
+            return False
+        return (type(emb.to_state[0]) is Linear and type(emb.to_state[1]) is Tanh and type(self.to_output[0]) is Linear
+                and emb.to_state[0].bias is not None and self.to_output[0].bias is not None and emb.embedding_dims <= 20)
+
+    def forward(self, feats, targets=None):
+        if not self.fused():
+            return super().forward(feats, targets=targets)
+        feats = TF.sum_hw(run_layers(self.activation, feats))
+        if isinstance(feats, TF.Pair):
+            batch_size = feats.r.shape[0]
+            q_real = self.iqn.sample_quantiles(batch_size)
+            taus = TF.Pair(q_real, self.iqn.sample_quantiles(batch_size))
+        else:
+            taus = self.iqn.sample_quantiles(feats.shape[0])
+        emb, out = self.iqn.quantile_embedding, self.to_output[0]
+        p_target, loss = TF.iqn_head(feats, taus, targets, emb.to_state[0].weight, emb.to_state[0].bias, out.weight, out.bias,
+                                     emb.embedding_range, self.iqn.num_quantiles)
         if targets is not None:
             return p_target, loss
         return p_target

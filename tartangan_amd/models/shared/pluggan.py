@@ -3,13 +3,16 @@
 A ``SharedModel`` owns ONE filter bank, ``shared_filters[max(blocks), max(latent_dims, *blocks), 3, 3]``, and hands it to every
 block it builds; the factories are called with exactly the reference's arguments.  Construction consumes the init RNG like the
 reference: the ``randn * 0.01`` draw first, which ``xavier_uniform_`` (gain of 'relu') then overwrites, then the blocks in
-order.  ``SharedIQNDiscriminator`` is not implemented.
+order.  ``SharedIQNDiscriminator`` (pluggan.py:126-156) keeps its head outside the Sequential, as ``to_output``, and hands it
+the targets; its default head is the fused one (``FusedIQNDiscriminatorOutput``).
 """
 import torch
 from torch import nn
 
 from ... import functional as TF
-from ..blocks import DiscriminatorInput, DiscriminatorOutput, GeneratorInputMLP, GeneratorOutput, SelfAttention2d
+from ..blocks import (
+    DiscriminatorInput, DiscriminatorOutput, FusedIQNDiscriminatorOutput, GeneratorInputMLP, GeneratorOutput, SelfAttention2d,
+)
 from .blocks import SharedConvBlock, SharedResidualGeneratorBlock
 
 
@@ -84,6 +87,12 @@ class SharedDiscriminator(SharedModel):
     default_output = DiscriminatorOutput
 
     def build(self):
+        stages, out_dims = self._stages()
+        stages.append(self.output_factory(out_dims, 1))
+        self.blocks = nn.Sequential(*stages)
+
+    def _stages(self):
+        """-> (from-RGB and the blocks, the width they end at)"""
         cfg = self.config
         in_dims = cfg.blocks[-1]
         stages = [self.input_factory(cfg.data_dims, in_dims)]
@@ -95,5 +104,22 @@ class SharedDiscriminator(SharedModel):
             if self._wants_attention(block_i):
                 stages.append(SelfAttention2d(out_dims))
             in_dims = out_dims
-        stages.append(self.output_factory(in_dims, 1))
+        return stages, in_dims
+
+
+class SharedIQNDiscriminator(SharedDiscriminator):
+    """pluggan.py:126-156: the blocks in ``self.blocks``, the head beside them as ``self.to_output`` (registered after the blocks,
+    like the reference); ``forward(x, targets=None)`` -> ``p_target`` or ``(p_target, loss)``.  A ``Pair`` runs blocks and head
+    alike on 2B images; the head draws each half's taus separately, real first."""
+    default_output = FusedIQNDiscriminatorOutput
+
+    def build(self):
+        stages, out_dims = self._stages()
         self.blocks = nn.Sequential(*stages)
+        self.to_output = self.output_factory(out_dims, 1)
+
+    def forward(self, x, targets=None):
+        if TF.filter_forms_active():
+            return self.to_output(self._run_blocks(x), targets=targets)
+        with TF.filter_forms():
+            return self.to_output(self._run_blocks(x), targets=targets)

@@ -20,6 +20,8 @@ from .. import cnn as _cnn
 
 
 class CNNTrainer(_cnn.CNNTrainer):
+    discriminator_class = SharedDiscriminator
+
     def _factories(self):
         f = super()._factories()
         bound = dict(norm_factory={'id': nn.Identity, 'bn': BatchNorm2d}[self.args.norm],
@@ -40,7 +42,7 @@ class CNNTrainer(_cnn.CNNTrainer):
         # construction order g, target_g, d consumes the init RNG like the reference (shared/cnn.py:66-83)
         self.g = make_g()
         self.target_g = make_g()
-        self.d = SharedDiscriminator(self.gan_config, block_factory=f['d_block'], output_factory=f['d_output']).to(self.device)
+        self.d = self.discriminator_class(self.gan_config, block_factory=f['d_block'], output_factory=f['d_output']).to(self.device)
         self.optimizer_g = FusedAdam(self.g, lr=self.args.lr_g, betas=(0., 0.999))
         self.optimizer_d = FusedAdam(self.d, lr=self.args.lr_d, betas=(0., 0.999))
         if self.args.activation == 'selu':
