@@ -167,7 +167,8 @@ int tg_channel_bcast(const float* v, float* out, int B, int C, int HW, void* str
 /* ---------------------------------------------------------------- GEMM
  * nn.Linear (generator.py:70-72, discriminator.py:137-139,158-160, iqn.py:33-35)
  * and torch.bmm (attention.py:32,34).  Row-major; C[b] = op(A[b]) op(B[b]) (+ bias[n]) + beta*C[b].
- * op(A) is MxK, op(B) is KxN; lda/ldb/ldc are row strides of the stored arrays. */
+ * op(A) is MxK, op(B) is KxN; lda/ldb/ldc are row strides of the stored arrays.  The batch sits on a grid dimension:
+ * batch > 65535 is TG_EUNSUPPORTED, nothing launched (the caller slices the batch). */
 int tg_gemm(const float* A, const float* Bm, float* C, const float* bias_n /*nullable*/,
             int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB,
             int batch, int64_t strideA, int64_t strideB, int64_t strideC, float beta, void* stream);
@@ -374,7 +375,9 @@ int tg_softmax_dbwd(const float* v, const float* gy, const float* y, float* out,
  * o = g softmax_m(theta^T phi)^T without materialising the (N x M) map.
  * theta (B,D,N), phi (B,D,M), g (B,DV,M), o (B,DV,N), lse (B,N) = log sum_m exp(score).
  * Compiled for (D,DV) in {(1,4),(2,8),(4,16),(8,32),(16,64)} (C = 8..128); others: TG_EUNSUPPORTED
- * (the host then composes tg_gemm / tg_softmax_*).  _bwd is the first-order backward;
+ * (the host then composes tg_gemm / tg_softmax_*).  The images sit on a grid dimension: B > 65535 is TG_EUNSUPPORTED for
+ * tg_attn_fwd, tg_attn_bwd and tg_attn_dbwd alike, nothing launched or written (compose, in slices of the batch).
+ * _bwd is the first-order backward;
  * workspace: tg_attn_bwd_workspace() bytes.  Second order (the R1 penalty differentiates _bwd): the
  * host forms the (N x M) maps with tg_gemm and calls tg_attn_dbwd_rows for everything row-wise.       */
 int tg_attn_supported(int D, int DV);

@@ -726,7 +726,7 @@ int tg_attn_dbwd(const float* go, const float* theta, const float* phi, const fl
   TG_CHECK_PTR(d_go); TG_CHECK_PTR(d_theta); TG_CHECK_PTR(d_phi); TG_CHECK_PTR(d_g); TG_CHECK_PTR(workspace);
   TG_CHECK_POS(B); TG_CHECK_POS(N); TG_CHECK_POS(M);
   if (!tg_attn_dbwd_supported(D, DV, M)) return TG_EUNSUPPORTED;
-  if (B > 65535) return TG_EINVAL;
+  if (B > 65535) return TG_EUNSUPPORTED;              // the images sit on gridDim.y, as in tg_attn_fwd / tg_attn_bwd
   const int cpl = dbwd_cpl(D, DV, M);
   hipStream_t st = tg_stream(stream);
 #define TG_DBWD(D_, DV_) \

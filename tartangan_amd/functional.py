@@ -1294,8 +1294,7 @@ class _Gemm(Function):
         if A.dim() == 2 and ta and not tb:
             _gemm_tn_into(A, Bm, C, accumulate=False)
         else:
-            K().gemm(A, Bm, C, None, M, N, Kd, ac, bc, N, int(ta), int(tb), batch,
-                     ar * ac, br * bc, M * N, 0.0)
+            _gemm_batches(A, Bm, C, M, N, Kd, ac, bc, int(ta), int(tb), batch, ar * ac, br * bc, 0.0)
         ctx.save_for_backward(A, Bm)
         ctx.ta, ctx.tb = ta, tb
         return C
@@ -1310,6 +1309,19 @@ class _Gemm(Function):
         if ctx.needs_input_grad[1]:
             gB = _Gemm.apply(g, A, True, ta) if tb else _Gemm.apply(A, g, not ta, False)
         return gA, gB, None, None
+
+
+GEMM_MAX_BATCH = 65535          # tg_gemm puts the batch on a grid dimension: TG_EUNSUPPORTED above this (as tg_attn_*)
+
+
+def _gemm_batches(A, Bm, C, M, N, Kd, lda, ldb, ta, tb, batch, sA, sB, beta):
+    """tg_gemm over `batch` products; more than GEMM_MAX_BATCH of them go in slices of the (contiguous) leading dimension."""
+    if batch <= GEMM_MAX_BATCH:
+        K().gemm(A, Bm, C, None, M, N, Kd, lda, ldb, N, ta, tb, batch, sA, sB, M * N, beta)
+        return
+    for b0 in range(0, batch, GEMM_MAX_BATCH):
+        b1 = min(batch, b0 + GEMM_MAX_BATCH)
+        K().gemm(A[b0:b1], Bm[b0:b1], C[b0:b1], None, M, N, Kd, lda, ldb, N, ta, tb, b1 - b0, sA, sB, M * N, beta)
 
 
 def matmul(A, Bm, transA=False, transB=False):
@@ -2481,7 +2493,7 @@ def _bgemm(A, Bm, ta=False, tb=False, out=None):
     beta = 1.0
     if out is None:
         out, beta = A.new_empty(batch, M, N), 0.0
-    K().gemm(A, Bm, out, None, M, N, Kd, ac, bc, N, int(ta), int(tb), batch, ar * ac, br * bc, M * N, beta)
+    _gemm_batches(A, Bm, out, M, N, Kd, ac, bc, int(ta), int(tb), batch, ar * ac, br * bc, beta)
     return out
 
 
@@ -2563,7 +2575,9 @@ class _AttnCore(Function):
 
 def attention_core(theta, phi, g):
     """theta (B,D,N), phi (B,D,M), g (B,DV,M) -> (B,DV,N).  Fused kernel when the head dims are compiled in."""
-    fused = K().attn_supported(theta.shape[1], g.shape[1])
+    # the fused kernels put the images on a grid dimension: above GEMM_MAX_BATCH of them they return TG_EUNSUPPORTED
+    images = theta.r.shape[0] + theta.f.shape[0] if _is_pair(theta) else theta.shape[0]
+    fused = K().attn_supported(theta.shape[1], g.shape[1]) and images <= GEMM_MAX_BATCH
     if _is_pair(theta):
         if fused:
             return pair_apply(_AttnCore, theta, phi, g)
