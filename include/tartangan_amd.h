@@ -554,6 +554,51 @@ int tg_scene_patches_bwd(const float* gout, const float* theta, const float* mas
                          const float* noise /*nullable*/, float* gtheta, float* gmask_logits /*nullable*/,
                          int B, int P, int patch, int S, void* stream);
 
+/* ---------------------------------------------------------------- text trainer (since version 105)
+ * nn.Conv1d(k=3, padding=1) / nn.Conv1d(k=1) over (B, C, L): the residual blocks of trainers/text_cnn.py:57-80 built with
+ * conv_factory=nn.Conv1d, L = 4 .. 64 tokens.  ks in {1, 3}, stride 1, zero padding ks / 2; x (B, Cin, L), w (Cout, Cin, ks).
+ * Implicit GEMMs on the fp32-input MFMA with the batch-flattened B * L token axis as the long side, so short sequences
+ * still fill tiles; a tile may span several sequences, and every sequence is zero-padded at ITS OWN ends.  Exact fp32, no
+ * atomics, bit-identical from run to run; pointers at any multiple of 4 bytes.  Other ks, or a shape whose 32-bit indexes
+ * would overflow (tg_conv1d_supported == 0): TG_EUNSUPPORTED, nothing written.
+ * tg_conv1d_wgrad: gw[co][ci][t] = sum_{b,l} gy[b][co][l] x[b][ci][l + t - ks/2] and, when gbias != NULL, gbias[co] =
+ * sum_{b,l} gy from the same pass; two stages (per-workgroup partials over slices of B * L in `workspace`, then a
+ * fixed-order sum); accumulate != 0 adds into gw / gbias; a workspace below tg_conv1d_wgrad_workspace(): TG_EWORKSPACE. */
+int tg_conv1d_supported(int B, int Cin, int Cout, int L, int ks);
+int tg_conv1d_fwd(const float* x, const float* w, const float* bias /*nullable*/, const float* residual /*nullable, shape of y*/,
+                  float* y, int B, int Cin, int Cout, int L, int ks, void* stream);
+int tg_conv1d_dgrad(const float* gy, const float* w, float* gx, int B, int Cin, int Cout, int L, int ks, void* stream);
+size_t tg_conv1d_wgrad_workspace(int B, int Cin, int Cout, int L, int ks);
+int tg_conv1d_wgrad(const float* x, const float* gy, float* gw, float* gbias /*nullable*/, float* workspace, size_t workspace_bytes,
+                    int B, int Cin, int Cout, int L, int ks, int accumulate, void* stream);
+/* F.interpolate(scale_factor=2) on (B, C, L) (generator.py:58) and nn.AvgPool1d(2) (discriminator.py:67), transposes of each
+ * other up to a factor:  up2x1d: y[bc][2l + d] = alpha * x[bc][l];  pool2_1d: y[bc][l] = residual + 0.5 (x[bc][2l] + x[bc][2l+1]).
+ * L is the length of the SHORT side for both (x of up2x1d, y of pool2_1d).  The discriminator block's
+ * F.interpolate(scale_factor=0.5, mode='linear', align_corners=False) on an even length is tg_pool2_1d exactly. */
+int tg_up2x1d(const float* x, float* y, float alpha, int BC, int L, void* stream);
+int tg_pool2_1d(const float* x, const float* residual /*nullable*/, float* y, int BC, int L, void* stream);
+/* One skip-gram step (models/text.py:42-55, its sparse backward + coalesce, torch.optim.SGD; trainers/text_cnn.py:162-182) in
+ * two launches.  U, V (vocab, E) are updated IN PLACE; words (B), contexts (B, C2), negatives (B, C2) int64.
+ *   loss_out[0] = -(1/B) sum_b sum_j [log sigmoid(V[ctx_bj] . U[w_b]) + log sigmoid(-V[neg_bj] . U[w_b])]
+ * from the tables as they were on entry (log sigmoid in its stable form: scores of +-90 give finite values and saturated
+ * gradients), then T[r] -= lr * g[r] for both tables, g from the pre-update values, all occurrences of a row summed in a
+ * fixed order (words in batch order; contexts in (b, j) order, then negatives).  Rows equal to padding_idx (< 0: none) and
+ * rows no index names stay bit-unchanged.  No atomics, bit-identical from run to run.
+ * An index outside [0, vocab) is NOT refused (that would need a device-to-host read) and is never dereferenced: it reads as
+ * a row of zeros and receives no update; callers that want the reference's IndexError check the indexes on the host.
+ * E > 1024 or 2 * B * C2 > 65536: TG_EUNSUPPORTED; U == V or a null pointer: TG_EINVAL; nothing written either way. */
+size_t tg_skipgram_workspace(int B, int C2, int E);
+int tg_skipgram_step(float* U, float* V, const int64_t* words, const int64_t* contexts, const int64_t* negatives, float lr,
+                     int padding_idx, float* loss_out, float* workspace, size_t workspace_bytes, int B, int C2, int E, int vocab,
+                     void* stream);
+/* embedding(idx).permute(0, 2, 1) (trainers/text_cnn.py:186): out[b][e][l] = U[idx[b][l]][e], copy-exact, rows read along e and
+ * written along l through an LDS tile.  An index outside [0, vocab) writes zeros. */
+int tg_embed_gather_t(const float* U, const int64_t* idx, float* out, int B, int L, int E, int vocab, void* stream);
+/* SkipGram.lookup (models/text.py:57-69): out[b][l] = argmax_{i >= 1} (U[i] . z[b, :, l]) / |U[i]|, z (B, E, L), out (B, L)
+ * int64.  The reference's quirk is kept: row 0 is skipped and the result counts from row 1 (0 means row 1).  First maximum
+ * on exact ties, NaN (a zero row) counts as largest, like torch.argmax.  vocab < 2: TG_EINVAL; E > 1024: TG_EUNSUPPORTED. */
+int tg_embed_lookup(const float* U, const float* z, int64_t* out, int B, int L, int E, int vocab, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline
  * ImageBytesDataset (image_bytes_dataset.py:12-49) + ToPILImage -> RandomCrop(size) -> ToTensor -> Normalize(.5, .5)
  * (trainers/trainer.py:69-78) for a whole batch: archive = device-resident uint8 (n_images, H, W, channels) exactly

@@ -9,7 +9,7 @@ hand-written HIP kernels only.  PyTorch supplies tensor storage and graph
 bookkeeping, nothing else.
 
 Linear ops come as transpose pairs (each is the other's backward):
-  conv2d fwd <-> dgrad, (wgrad bilinear);  up2x <-> pool2;  bilinear_half <-> its
+  conv2d fwd <-> dgrad, (wgrad bilinear);  conv1d likewise;  up2x <-> pool2 (and the 1-D pair);  bilinear_half <-> its
   transpose;  maxpool scatter <-> gather;  row_sum <-> row_bcast;
   repeat_rows <-> sum_reps;  channel_sum <-> channel_bcast.
 """
@@ -732,6 +732,211 @@ def conv2d(x, weight, bias=None, residual=None, residual_up=False):
 
 
 PAIR_SPECS[_ConvFwd] = ('b--b-', 'h--', 'b')
+
+
+# =========================================================================== conv1d (the text trainer's nn.Conv1d)
+class _Conv1dFwd(Function):
+    """y = conv1d(x, w) + bias [+ residual] over (B, C, L); same structure as ``_ConvFwd``: forward <-> dgrad are a transpose pair,
+    wgrad is bilinear, so the R1 penalty differentiates twice through the three tg_conv1d_* entry points only."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, residual=None):
+        x, w = x.contiguous(), w.contiguous()
+        B, Cin, L = x.shape
+        Cout, ks = w.shape[0], w.shape[2]
+        y = x.new_empty(B, Cout, L)
+        if residual is not None:
+            residual = residual.contiguous()
+        K().conv1d_fwd(x, w, bias, residual, y, B, Cin, Cout, L, ks)
+        ctx.save_for_backward(x, w, bias)
+        ctx.has_residual = residual is not None
+        ctx.data_input = is_data(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, bias = ctx.saved_tensors
+        gy = gy.contiguous()
+        gx = gw = gb = None
+        need_w = ctx.needs_input_grad[1] and _param_grads_wanted()
+        need_b = bias is not None and ctx.needs_input_grad[2] and _param_grads_wanted()
+        if ctx.needs_input_grad[0] and not _skip_input_grad(ctx):
+            gx = _Conv1dDgrad.apply(gy, w)
+        sink_w, sink_b = _grad_sink(w), _grad_sink(bias)
+        if need_w and sink_w is not None and (not need_b or sink_b is not None):
+            _conv1d_wgrad_into(x, gy, sink_w, sink_b if need_b else None, w.shape[2], accumulate=1)
+        else:
+            if need_w:
+                gw = _Conv1dWgrad.apply(x, gy, w.shape[2])
+            if need_b:
+                gb = _ChannelSum.apply(gy)
+        gres = gy if ctx.has_residual and ctx.needs_input_grad[3] else None
+        return gx, gw, gb, gres
+
+
+class _Conv1dDgrad(Function):
+    @staticmethod
+    def forward(ctx, gy, w):
+        gy, w = gy.contiguous(), w.contiguous()
+        B, Cout, L = gy.shape
+        Cin, ks = w.shape[1], w.shape[2]
+        gx = gy.new_empty(B, Cin, L)
+        K().conv1d_dgrad(gy, w, gx, B, Cin, Cout, L, ks)
+        ctx.save_for_backward(gy, w)
+        return gx
+
+    @staticmethod
+    def backward(ctx, v):
+        gy, w = ctx.saved_tensors
+        v = v.contiguous()
+        a_gy = a_w = None
+        if ctx.needs_input_grad[0]:
+            a_gy = _Conv1dFwd.apply(v, w, None, None)
+        if ctx.needs_input_grad[1]:
+            sink = _grad_sink(w) if _param_grads_wanted() else None
+            if sink is not None:
+                _conv1d_wgrad_into(v, gy, sink, None, w.shape[2], accumulate=1)
+            else:
+                a_w = _Conv1dWgrad.apply(v, gy, w.shape[2])
+        return a_gy, a_w
+
+
+def _conv1d_wgrad_into(x, gy, gw, gbias, ks, accumulate):
+    B, Cin, L = x.shape
+    Cout = gy.shape[1]
+    ws = _ws(x, K().conv1d_wgrad_workspace(B, Cin, Cout, L, ks))
+    K().conv1d_wgrad(x, gy, gw, gbias, ws, ws.numel() * 4, B, Cin, Cout, L, ks, accumulate)
+
+
+class _Conv1dWgrad(Function):
+    @staticmethod
+    def forward(ctx, x, gy, ks):
+        x, gy = x.contiguous(), gy.contiguous()
+        gw = x.new_empty(gy.shape[1], x.shape[1], ks)
+        _conv1d_wgrad_into(x, gy, gw, None, ks, accumulate=0)
+        ctx.save_for_backward(x, gy)
+        return gw
+
+    @staticmethod
+    def backward(ctx, vw):
+        x, gy = ctx.saved_tensors
+        vw = vw.contiguous()
+        a_x = a_gy = None
+        if ctx.needs_input_grad[0]:
+            a_x = _Conv1dDgrad.apply(gy, vw)
+        if ctx.needs_input_grad[1]:
+            a_gy = _Conv1dFwd.apply(x, vw, None, None)
+        return a_x, a_gy, None
+
+
+def conv1d(x, weight, bias=None, residual=None):
+    """k=3 (pad 1) or k=1 (pad 0) stride-1 nn.Conv1d over (B, C, L), fp32; optional fused ``+ residual``."""
+    if x.dim() != 3 or weight.dim() != 3 or weight.shape[2] not in (1, 3) or weight.shape[1] != x.shape[1]:
+        raise RuntimeError(f'conv1d: x {tuple(x.shape)} / weight {tuple(weight.shape)}: (B, Cin, L) and (Cout, Cin, 1 | 3) only')
+    return _Conv1dFwd.apply(x, weight, bias, residual)
+
+
+# =========================================================================== 1-D resampling
+class _Up2x1d(Function):
+    """y[.., 2l + d] = alpha * x[.., l]"""
+
+    @staticmethod
+    def forward(ctx, x, alpha):
+        x = x.contiguous()
+        B, C, L = x.shape
+        y = x.new_empty(B, C, 2 * L)
+        K().up2x1d(x, y, alpha, B * C, L)
+        ctx.alpha = alpha
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        # the transpose is alpha * (pair sum) = 2 alpha * tg_pool2_1d
+        p = _Pool2x1d.apply(g, None)
+        return (p if ctx.alpha == 0.5 else _Scale.apply(p, 2.0 * ctx.alpha)), None
+
+
+class _Pool2x1d(Function):
+    """0.5 * (x[.., 2l] + x[.., 2l + 1]) [+ residual]"""
+
+    @staticmethod
+    def forward(ctx, x, residual=None):
+        x = x.contiguous()
+        B, C, L = x.shape
+        if L % 2:
+            raise RuntimeError('avg_pool2_1d needs an even length')
+        y = x.new_empty(B, C, L // 2)
+        if residual is not None:
+            residual = residual.contiguous()
+        K().pool2_1d(x, residual, y, B * C, L // 2)
+        ctx.has_residual = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return _Up2x1d.apply(g, 0.5), (g if ctx.has_residual and ctx.needs_input_grad[1] else None)
+
+
+def upsample_nearest2x_1d(x):
+    """F.interpolate(x, scale_factor=2) for (B, C, L)"""
+    return _Up2x1d.apply(x, 1.0)
+
+
+def avg_pool2_1d(x, residual=None):
+    """nn.AvgPool1d(2) [+ residual]; also F.interpolate(scale_factor=0.5, mode='linear', align_corners=False) on an even length"""
+    return _Pool2x1d.apply(x, residual)
+
+
+# =========================================================================== embeddings (outside autograd)
+def _check_indexes(name, idx, vocab):
+    """The reference's IndexError, where it costs nothing: indexes still on the host.  (On the device the kernels never
+    dereference an index outside [0, vocab): it reads as a row of zeros.)"""
+    if not idx.is_cuda and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= vocab):
+        raise IndexError(f'{name}: index out of range [0, {vocab})')
+
+
+def embed_gather_t(table, idx):
+    """embedding(idx).permute(0, 2, 1) as one contiguous (B, E, L) tensor; no gradient (the reference detaches it)."""
+    _check_indexes('embed_gather_t', idx, table.shape[0])
+    table = table.detach().contiguous()
+    idx = idx.to(device=table.device, dtype=torch.int64).contiguous()
+    B, L = idx.shape
+    vocab, E = table.shape
+    out = table.new_empty(B, E, L)
+    K().embed_gather_t(table, idx, out, B, L, E, vocab)
+    return out
+
+
+def embed_lookup(table, z):
+    """SkipGram.lookup: (B, L) int64 = argmax over rows 1.. of the cosine-style score, counted from row 1 (the reference's quirk)."""
+    table, z = table.detach().contiguous(), z.detach().contiguous()
+    B, E, L = z.shape
+    if table.shape[1] != E:
+        raise RuntimeError(f'embed_lookup: z has {E} dims, the table {table.shape[1]}')
+    out = torch.empty(B, L, dtype=torch.int64, device=z.device)
+    K().embed_lookup(table, z, out, B, L, E, table.shape[0])
+    return out
+
+
+def skipgram_step(U, V, words, contexts, negatives, lr, padding_idx=None, loss_out=None):
+    """One fused skip-gram step: the loss of the tables as they are (a device scalar), then plain SGD on both IN PLACE."""
+    vocab, E = U.shape
+    for name, idx in (('words', words), ('contexts', contexts), ('negatives', negatives)):
+        _check_indexes('skipgram_step ' + name, idx, vocab)
+    if not (U.is_contiguous() and V.is_contiguous()) or U.shape != V.shape:
+        raise RuntimeError('skipgram_step: two contiguous tables of one shape')
+    dev = U.device
+    words, contexts, negatives = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (words, contexts, negatives))
+    B, C2 = contexts.shape
+    if tuple(words.shape) != (B,) or tuple(negatives.shape) != (B, C2):
+        raise RuntimeError('skipgram_step: words (B), contexts (B, C2), negatives (B, C2)')
+    if loss_out is None:
+        loss_out = torch.empty((), dtype=U.dtype, device=dev)
+    ws = _ws(U, K().skipgram_workspace(B, C2, E))
+    with torch.no_grad():
+        K().skipgram_step(U, V, words, contexts, negatives, float(lr), -1 if padding_idx is None else int(padding_idx), loss_out, ws,
+                          ws.numel() * 4, B, C2, E, vocab)
+    return loss_out
 
 
 # =========================================================================== from-RGB 1x1 composed into the first 3x3
@@ -1989,6 +2194,11 @@ def sum_hw(x):
 
 
 PAIR_SPECS[_RowSum] = ('b--', '', 'b')          # (only for reductions that keep the image dimension)
+
+
+def sum_tail(x, nd):
+    """torch.sum over the trailing ``nd`` dimensions ((B, C, L) -> (B, C) with nd = 1: the text discriminator's sum pool)"""
+    return _RowSum.apply(x, nd, 1.0)
 
 
 class _RepeatRows(Function):

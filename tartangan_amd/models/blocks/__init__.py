@@ -4,6 +4,6 @@ from .discriminator import (  # noqa
     ResidualDiscriminatorBlock,
 )
 from .generator import (  # noqa
-    GeneratorInputMLP, GeneratorOutput, ResidualGeneratorBlock, TiledZGeneratorInput,
+    GeneratorInputMLP, GeneratorInputMLP1d, GeneratorOutput, ResidualGeneratorBlock, TiledZGeneratorInput,
 )
 from .scene import SceneStructureBlock  # noqa

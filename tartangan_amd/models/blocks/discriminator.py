@@ -112,7 +112,11 @@ class DiscriminatorOutput(nn.Module):
         self.to_output = nn.Sequential(Linear(in_dims, out_dims), output_activation_factory())
 
     def forward(self, feats):
-        feats = TF.sum_hw(run_layers(self.activation, feats))
+        feats = run_layers(self.activation, feats)
+        # the sum over every dimension behind the channels (discriminator.py:143-144): (H, W), or L for the text trainer
+        if TF._is_pair(feats) and feats.r.dim() != 4:
+            raise NotImplementedError('DiscriminatorOutput: a Pair of (B, C, L) halves (the shared real | fake pass is 2-D only)')
+        feats = TF.sum_tail(feats, 1) if not TF._is_pair(feats) and feats.dim() == 3 else TF.sum_hw(feats)
         return run_layers(self.to_output, feats)
 
 

@@ -62,7 +62,10 @@ class ResidualGeneratorBlock(nn.Module):
             if type(conv) is Conv2d and conv.kernel_size == (3, 3) and len(mods) > 3 and TF.upconv3x3_pays(a, conv.weight):
                 return run_layers(self.convs[3:], TF.upconv3x3(a, conv.weight, conv.bias), residual=shortcut, residual_up=True)
             return run_layers(self.convs[2:], TF.upsample_nearest2x(a), residual=shortcut, residual_up=True)
-        xs, xu = TF.fork_upsample_nearest2x(x)           # one graph node for both uses (functional._ForkUp2x)
+        if not TF._is_pair(x) and x.dim() == 3:          # (B, C, L), the text trainer: the two uses of up(x) meet in autograd
+            xs = xu = TF.upsample_nearest2x_1d(x)
+        else:
+            xs, xu = TF.fork_upsample_nearest2x(x)       # one graph node for both uses (functional._ForkUp2x)
         shortcut = xs if self.project_input is None else run_layers(self.project_input, xs)
         return run_layers(self.convs, xu, residual=shortcut)
 
@@ -79,6 +82,20 @@ class GeneratorInputMLP(nn.Module):
 
     def forward(self, z):
         return run_layers(self.base_img, z).view(-1, self.output_dims, self.size, self.size)
+
+
+class GeneratorInputMLP1d(nn.Module):
+    """z -> Linear -> act -> (B, C0, size): generator.py:83-98, the text trainer's --g-base mlp (sub-module name ``base``)."""
+
+    def __init__(self, latent_dims, output_dims, size=4, norm_factory=None, activation_factory=_lrelu):
+        super().__init__()
+        self.base = nn.Sequential(Linear(latent_dims, size * output_dims), activation_factory())
+        self.latent_dims = latent_dims
+        self.output_dims = output_dims
+        self.size = size
+
+    def forward(self, z):
+        return run_layers(self.base, z).view(-1, self.output_dims, self.size)
 
 
 class TiledZGeneratorInput(nn.Module):

@@ -126,6 +126,48 @@ class BatchNorm2d(nn.BatchNorm2d):
         return self._run(x, slope, replicate)
 
 
+class Conv1d(nn.Conv1d):
+    """nn.Conv1d as the text trainer's blocks use it (conv_factory=nn.Conv1d): k=3/pad 1 or k=1/pad 0, stride 1, over (B, C, L)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, padding=0, bias=True, **kw):
+        super().__init__(in_channels, out_channels, kernel_size, padding=padding, bias=bias, **kw)
+        ks = self.kernel_size
+        ok = (ks in ((1,), (3,)) and self.padding == (ks[0] // 2,) and self.stride == (1,) and self.dilation == (1,) and self.groups == 1)
+        if not ok:
+            raise ValueError(f'tartangan_amd.Conv1d supports k=3/pad1 and k=1/pad0 stride-1 only, got {self}')
+
+    def forward(self, x, residual=None):
+        return TF.conv1d(x, self.weight, self.bias, residual)
+
+
+class AvgPool1d(nn.AvgPool1d):
+    def __init__(self, kernel_size, **kw):
+        super().__init__(kernel_size, **kw)
+        if kernel_size not in (2, (2,)):
+            raise ValueError('tartangan_amd.AvgPool1d supports kernel_size=2 only')
+
+    def forward(self, x, residual=None):
+        return TF.avg_pool2_1d(x, residual)
+
+
+class BatchNorm1d(nn.BatchNorm1d):
+    """nn.BatchNorm1d over (B, C, L) through the BatchNorm entry points with HW = L; ``forward_act`` as ``BatchNorm2d``."""
+
+    def _run(self, x, slope):
+        if self.momentum is None or not self.affine or not self.track_running_stats:
+            raise NotImplementedError('tartangan_amd.BatchNorm1d: default nn.BatchNorm1d options only')
+        if x.dim() != 3:
+            raise NotImplementedError('tartangan_amd.BatchNorm1d takes (B, C, L)')
+        return TF.batch_norm_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.training, self.momentum,
+                                 self.eps, slope, self.num_batches_tracked if self.training else None)
+
+    def forward(self, x):
+        return self._run(x, 1.0)
+
+    def forward_act(self, x, slope):
+        return self._run(x, slope)
+
+
 def run_layers(seq, x, residual=None, residual_up=False):
     """Apply an ``nn.Sequential`` the way ``Sequential.forward`` would, fusing each
     (BatchNorm2d, LeakyReLU) pair into one kernel pass.  ``residual`` (the block's shortcut) is added to the
@@ -139,7 +181,12 @@ def run_layers(seq, x, residual=None, residual_up=False):
     while i < len(mods):
         m = mods[i]
         last = i == len(mods) - 1
-        if (isinstance(m, BatchNorm2d) and i + 1 < len(mods) and isinstance(mods[i + 1], LeakyReLU)):
+        if last and residual is not None and type(m) in (Conv1d, AvgPool1d):
+            # (B, C, L), the text trainer: the shortcut add rides in the 1-D kernel's epilogue
+            x, residual = m(x, residual), None
+            i += 1
+            continue
+        if (isinstance(m, (BatchNorm2d, BatchNorm1d)) and i + 1 < len(mods) and isinstance(mods[i + 1], LeakyReLU)):
             x = m.forward_act(x, mods[i + 1].negative_slope)
             i += 2
             continue
@@ -176,6 +223,17 @@ class Interpolate(nn.Module):
 
 def interpolate(x, size=None, scale_factor=None, mode='nearest', align_corners=None):
     """F.interpolate for (scale 2, nearest), (scale .5, bilinear, align_corners=True) and (scale 2, bilinear, align_corners=True)."""
+    if not TF._is_pair(x) and x.dim() == 3:
+        # (B, C, L), the text trainer: nearest x2, and the discriminator block's linear x0.5 without align_corners, which on an
+        # even length is the average of each pair of tokens
+        if size is None and scale_factor == 2 and mode == 'nearest':
+            return TF.upsample_nearest2x_1d(x)
+        if size is None and scale_factor == 0.5 and mode == 'linear' and not align_corners:
+            if x.shape[2] % 2:
+                raise NotImplementedError('interpolate(scale_factor=0.5, mode="linear") needs an even length')
+            return TF.avg_pool2_1d(x)
+        raise NotImplementedError(f'interpolate(scale_factor={scale_factor}, mode={mode}, align_corners={align_corners}) on (B, C, L) '
+                                  f'is outside the hot path')
     if size is None and scale_factor == 2 and mode == 'nearest':
         return TF.upsample_nearest2x(x)
     if size is None and scale_factor == 2 and mode == 'bilinear' and align_corners:

@@ -52,6 +52,7 @@ class RngFeed:
         self.cursor = 0
         self.key = None         # batch shape the plan was recorded for
         self.cat_dims = 0       # width of the categorical code of kind 'zc'
+        self.num_items = 0      # vocabulary size of kind 'negatives'
         self._spec = None       # (host generator states before, after) a speculative draw of the next step's inputs
         self._uploaded = None   # event behind the last host -> device copies of the staging buffers
         self._arena = self._host_arena = None   # one allocation behind all of an adopted plan's buffers
@@ -66,6 +67,12 @@ class RngFeed:
             return full[self.rank * rows:(self.rank + 1) * rows]
         if kind == 'noise':
             return torch.randn(rows, cols)
+        if kind == 'offsets':
+            # window offsets of the text trainer (text_cnn.py:168): ``np.random.randint(0, cols, rows)``, numpy's GLOBAL generator
+            return torch.from_numpy(np.random.randint(0, cols, rows).astype(np.int64))
+        if kind == 'negatives':
+            # SkipGram.loss's ``randint_like(context, 0, num_items)`` (models/text.py:50): (rows, cols) int64 below ``self.num_items``
+            return torch.randint(0, self.num_items, (rows, cols))
         # tau: (Q*B_global, 1) with row = q*B_global + b  ->  this rank's (Q*B, 1)
         q = cols
         full = torch.rand(rows * self.world, 1)
@@ -74,7 +81,12 @@ class RngFeed:
 
     def draw(self, kind, rows, cols):
         """kind 'z': (rows, cols) normal;  kind 'tau': (rows, 1) uniform with cols = num_quantiles;  kind 'noise': (rows, cols)
-        normal, the same on every rank;  kind 'zc': 'z' with the one-hot categorical code in its first ``cat_dims`` columns."""
+        normal, the same on every rank;  kind 'zc': 'z' with the one-hot categorical code in its first ``cat_dims`` columns;  the
+        integer kinds 'offsets' ((rows,) below cols, from numpy) and 'negatives' ((rows, cols) below ``num_items``) are int64 and
+        exist for inline drawing only (mode 'off': the text trainer, which does not replay from graphs) -- ``adopt`` / ``refill``
+        lay plans out in one float arena and do not take them."""
+        if kind in ('offsets', 'negatives') and self.mode != 'off':
+            raise NotImplementedError(f"RngFeed kind {kind!r} is drawn inline only (mode 'off')")
         if self.mode == 'off':
             return self._draw_cpu(kind, rows, cols).contiguous().to(self.device)
         if self.mode == 'record':
