@@ -611,6 +611,42 @@ int tg_image_bytes_batch(const uint8_t* archive, const int64_t* index, const int
                          const int* crop_x /*nullable*/, float* out, int B, int64_t n_images, int H, int W,
                          int channels, int size, void* stream);
 
+/* ---------------------------------------------------------------- explore apps (tartangan_amd/explore/, csrc/explore.hip; tg_version 106)
+ * All three: fp32, no atomics, sums in a fixed order (bit-identical between runs); every pointer may sit at any multiple of its
+ * element size; a bad argument returns before anything is launched or written.
+ *
+ * find_image.py:59-68 without --vgg: the reconstruction loss of generator output against a normalised target and its image gradient.
+ * imgs, target, grad_imgs: (B, 3, HW).  With mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225) (find_image.py:99-100):
+ *   d = ((x + 1) / 2 - mean_c) / std_c - t
+ *   kind 0 (nn.MSELoss(reduction='sum')):       *loss_out = sum d^2,       rho'(d) = 2 d
+ *   kind 1 (nn.SmoothL1Loss(reduction='sum')):  *loss_out = sum (|d| < 1 ? d^2 / 2 : |d| - 1/2),   rho'(d) = |d| < 1 ? d : sign(d)
+ *   grad_imgs = rho'(d) / (2 std_c)             (nullable: the loss alone, e.g. an L-BFGS closure's re-evaluations)
+ * At most two launches (one when B*3*HW <= 1024).  workspace: tg_recon_loss_workspace(B, C, HW) bytes, NaN-safe (written before
+ * read); smaller: TG_EWORKSPACE.  C != 3, another kind, B or HW < 1, a null imgs / target / loss_out: TG_EINVAL.  The query
+ * returns 0 for arguments tg_recon_loss refuses.                                                                             */
+size_t tg_recon_loss_workspace(int B, int C, int HW);
+int tg_recon_loss(const float* imgs, const float* target, float* grad_imgs /*nullable*/, float* loss_out, float* workspace,
+                  size_t workspace_bytes, int B, int C, int HW, int kind, void* stream);
+/* Everything a find-image step does to the latents after the backward pass (find_image.py:56-86), ONE launch of one workgroup over
+ * n = num_samples * latent_dims elements.  In this order:
+ *   1. stats[0] = *recon_loss + l2 * mean(z^2)                 the reported loss, from z before the update
+ *   2. g = gz + 2 l2 z / n
+ *   3. opt 0: torch.optim.Adam's default update of z (no weight decay, no amsgrad, bias correction from the counter *step, which
+ *      lives on the device: this launch uses *step + 1 and stores it, so the launch replays from a graph unchanged);
+ *      opt 1: z -= lr g                                        (m, v, step are not touched and may be null)
+ *   4. stats[1], stats[2], stats[3] = min, mean, max of the updated z   (min and max are NaN when z holds one, as torch's)
+ *   5. noise_next != null: z = noise_next where z > 3 or z < -3, strictly (find_image.py:77-81, the clip in front of the NEXT
+ *      step); NaN is not clipped.
+ * opt 2 does 5. alone (the clip in front of the first step): z and noise_next only, every other pointer may be null.
+ * z, m, v and *step are updated in place.  n < 1, another opt, a beta outside [0, 1), a null pointer the opt needs: TG_EINVAL. */
+int tg_latent_step(float* z, const float* gz, float* m, float* v, int64_t* step, const float* noise_next /*nullable*/,
+                   float* stats, const float* recon_loss, int64_t n, int opt, double lr, double beta1, double beta2, double eps,
+                   double l2, void* stream);
+/* continuous_interp.py:36-52 as one gather.  imgs: (rows * cols, C, h, w), out: (C, S, S):
+ *   out[c][y][x] = imgs[(y * rows) / S * cols + (x * cols) / S][c][(y * h) / S][(x * w) / S]        (integer division)
+ * which equals the reference's int(a * b / S) for every index in range.  Copy-exact.  A non-positive dimension: TG_EINVAL.   */
+int tg_mosaic_gather(const float* imgs, float* out, int rows, int cols, int C, int h, int w, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

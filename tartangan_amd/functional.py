@@ -3170,3 +3170,99 @@ class _SumSq(Function):
 
 def sumsq(x, alpha=1.0):
     return _SumSq.apply(x, float(alpha))
+
+
+# ---------------------------------------------------------------------------------------------------- explore apps (csrc/explore.hip)
+RECON_KINDS = {'mse': 0, 'l1': 1}
+
+
+def _check_fp32(name, *tensors):
+    """The explore kernels read raw fp32 pointers: a device tensor of another dtype would be misread silently.  (Host tensors
+    only ever reach a stand-in backend of the tests, which computes in the dtype it is given.)"""
+    for t in tensors:
+        if t is not None and t.is_cuda and t.dtype != torch.float32:
+            raise TypeError(f'{name}: expected float32 tensors, got {t.dtype}')
+
+
+def recon_loss_into(imgs, target, grad_imgs, loss_out, kind):
+    """tg_recon_loss on contiguous (B, 3, H, W) tensors: the loss into the 0-d / 1-element ``loss_out``, the image gradient into
+    ``grad_imgs`` (None: the loss alone)."""
+    if imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.shape != target.shape:
+        raise ValueError(f'recon_loss: images {tuple(imgs.shape)} / target {tuple(target.shape)}: need two equal (B, 3, H, W) tensors')
+    _check_fp32('recon_loss', imgs, target, grad_imgs, loss_out)
+    B, C, HW = imgs.shape[0], 3, imgs.shape[2] * imgs.shape[3]
+    nbytes = K().recon_loss_workspace(B, C, HW)
+    K().recon_loss(imgs, target, grad_imgs, loss_out, _ws(imgs, nbytes), nbytes, B, C, HW, kind)
+    return loss_out
+
+
+class _ReconLossBwd(Function):
+    """g * d loss / d imgs.  ``imgs`` is an input only so that a second differentiation arrives here and is refused, instead of
+    silently treating the stored gradient as a constant."""
+
+    @staticmethod
+    def forward(ctx, g, dimgs, imgs):
+        out = torch.empty_like(dimgs)
+        K().scale_dev(g.contiguous(), 1.0, dimgs, out, dimgs.numel())
+        return out
+
+    @staticmethod
+    def backward(ctx, gg):
+        raise NotImplementedError('recon_loss is first order only: no double backward through the reconstruction loss')
+
+
+class _ReconLoss(Function):
+    """find_image.py:59-68 without --vgg: the normalisation and the summed loss in one pass, the image gradient with it."""
+
+    @staticmethod
+    def forward(ctx, imgs, target, kind):
+        ic, target = imgs.contiguous(), target.contiguous()
+        loss = ic.new_empty(())
+        dimgs = torch.empty_like(ic) if ctx.needs_input_grad[0] else None
+        recon_loss_into(ic, target, dimgs, loss, kind)
+        ctx.save_for_backward(dimgs, imgs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dimgs, imgs = ctx.saved_tensors
+        return _ReconLossBwd.apply(g, dimgs, imgs), None, None
+
+
+def recon_loss(imgs, target, kind='mse'):
+    """``nn.MSELoss(reduction='sum')`` (kind 'mse' / 0) or ``nn.SmoothL1Loss(reduction='sum')`` ('l1' / 1) of the generator output
+    ``imgs`` in (-1, 1), mapped to [0, 1] and normalised with the ImageNet mean and std, against the already normalised ``target``.
+    Differentiable once, with respect to ``imgs`` only."""
+    if target.requires_grad:
+        raise ValueError('recon_loss: the target takes no gradient')
+    return _ReconLoss.apply(imgs, target, RECON_KINDS.get(kind, kind))
+
+
+LATENT_OPTS = {'adam': 0, 'sgd': 1, 'clip': 2}
+
+
+def latent_step(z, gz, m, v, step, noise_next, stats, recon, opt, lr=0.5, betas=(0.9, 0.999), eps=1e-8, l2=0.):
+    """tg_latent_step in place on ``z`` (and ``m``, ``v``, ``step`` for Adam): see include/tartangan_amd.h."""
+    _check_fp32('latent_step', z, gz, m, v, noise_next, stats, recon)
+    if step is not None and step.dtype != torch.int64:
+        raise TypeError(f'latent_step: the step counter is an int64 tensor, got {step.dtype}')
+    K().latent_step(z, gz, m, v, step, noise_next, stats, recon, z.numel(), LATENT_OPTS.get(opt, opt), float(lr), float(betas[0]),
+                    float(betas[1]), float(eps), float(l2))
+    return z
+
+
+def mosaic_index(a, b, size):
+    """Where output coordinate ``a`` of ``size`` reads along an axis of extent ``b``: the integer form tg_mosaic_gather uses of
+    continuous_interp.py:40-52's ``int(a * b / size)`` (equal for every index in range, tests/test_explore.py).  Ints or arrays."""
+    return (a * b) // size
+
+
+def mosaic_gather(imgs, rows, cols, size):
+    """(rows * cols, C, h, w) grid images -> the (C, size, size) mosaic of continuous_interp.py:36-52, one launch."""
+    n, C, h, w = imgs.shape
+    if n != rows * cols:
+        raise ValueError(f'mosaic_gather: {n} images for a {rows} x {cols} grid')
+    _check_fp32('mosaic_gather', imgs)
+    out = imgs.new_empty(C, size, size)
+    K().mosaic_gather(imgs.contiguous(), out, rows, cols, C, h, w, size)
+    return out
