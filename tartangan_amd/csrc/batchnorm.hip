@@ -7,8 +7,6 @@
 //   fwd : z = y*s
 //   bwd : gbeta = S(gyh); ggamma = S(gyh*xhat); gx = gamma*invstd*(gyh - gbeta/n - xhat*ggamma/n)
 //   dbwd: see tg_bn_act_dbwd below (derivation in DESIGN.md "BatchNorm second backward").
-#include <stdlib.h>
-
 #include "planes.h"
 
 namespace {
@@ -444,15 +442,7 @@ static inline int chan_grid(int C) { return (C + 63) / 64; }
 // pure launch latency (~20 us for a few hundred KB).  One kernel, one workgroup per channel: reduce, then apply
 // (the second read hits L2).  Same arithmetic as the large path (fp32 per-thread partials, fp64 combine).
 constexpr int SMALL_N = 16384;
-static inline int small_n_limit() {            // TG_BN_SMALL_N: development knob (<= SMALL_N), read once
-  static const int v = [] {
-    const char* e = getenv("TG_BN_SMALL_N");
-    const int k = e ? atoi(e) : SMALL_N;
-    return k < 0 ? 0 : (k > SMALL_N ? SMALL_N : k);
-  }();
-  return v;
-}
-static inline bool small_case(int B, int C, int HW) { return (int64_t)B * HW <= small_n_limit() && C >= 8; }
+static inline bool small_case(int B, int C, int HW) { return (int64_t)B * HW <= SMALL_N && C >= 8; }
 
 // 1024 threads per channel, <= 16 elements per thread held in registers between the reduce and the apply pass:
 // every global load of a thread is issued up front (independent), nothing is read twice.

@@ -35,7 +35,7 @@ constexpr int CT_THREADS = 256;
 template <int TH_, int TW_, int NI_>
 struct Geo {
   static constexpr int TH = TH_, TW = TW_, NI = NI_, NPIX = TH_ * TW_ * NI_;
-  static_assert(NPIX == 512 || NPIX == 256 || NPIX == 64, "a pixel tile is 512 / 256 pixels (waves split pixels) or 64 (waves split K)");
+  static_assert(NPIX == 256 || NPIX == 64, "a pixel tile is 256 pixels (waves split pixels) or 64 (waves split K)");
   static constexpr int PPW = (NPIX == 64) ? 64 : NPIX / 4;     // pixels per wave
   static_assert(TW_ % 4 == 0, "rows are staged as float4");
 };
@@ -46,8 +46,6 @@ using GX = Geo<8, 32, 1>;
 using G4k = Geo<4, 4, 4>;
 using G8k = Geo<8, 8, 1>;
 using G16k = Geo<4, 16, 1>;
-using GX2 = Geo<16, 32, 1>;     // 512-pixel tiles of the LDS-DMA kernel (conv_dma_kernel)
-using G16x2 = Geo<16, 16, 2>;
 
 // Kernel-size codes: 1 = 1x1; 3 = 3x3 pad 1; 2 = a 2x2 window of taps INSIDE the 3x3 halo (one output phase of
 // conv3x3(nearest_up2x(.)), see tg_upconv3x3_*): patch geometry of the 3x3 kernel, 4 taps starting at (oy, ox).
@@ -618,33 +616,7 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, float* lds_wa
 
 #include "wino.h"
 
-#ifdef TG_DIAG_STAMPS
-// Diagnostic build (make -C tartangan_amd/csrc diag -> libtartangan_amd_diag.so, loaded with TG_LIBRARY=...): every workgroup
-// of conv_dma_kernel leaves (shader cycles, 100 MHz ticks) of its main loop here; nothing else reads this buffer and no
-// output depends on it.  tools/clock_probe.py turns it into the clock the chip holds under the kernel.
-#define TG_DIAG_SLOTS 8192
-__device__ unsigned long long tg_diag_stamps[2 * TG_DIAG_SLOTS];
-extern "C" int tg_diag_read_stamps(unsigned long long* host, int n_slots) {
-  if (n_slots > TG_DIAG_SLOTS) return -1;
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(tg_diag_stamps), sizeof(unsigned long long) * 2 * n_slots);
-}
-__device__ unsigned long long tg_diag_phases[16 * TG_DIAG_SLOTS];
-extern "C" int tg_diag_read_phases(unsigned long long* host, int n_slots) {
-  if (n_slots > TG_DIAG_SLOTS) return -1;
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(tg_diag_phases), sizeof(unsigned long long) * 16 * n_slots);
-}
-__device__ unsigned long long tg_diag_life[16 * TG_DIAG_SLOTS];
-extern "C" int tg_diag_read_life(unsigned long long* host, int n_slots) {
-  if (n_slots > TG_DIAG_SLOTS) return -1;
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(tg_diag_life), sizeof(unsigned long long) * 16 * n_slots);
-}
-extern "C" int tg_diag_clear_stamps() {
-  static unsigned long long zeros[2 * TG_DIAG_SLOTS];
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(tg_diag_stamps), zeros, sizeof(zeros));
-}
-#endif
-
-template <class G, int MF, int MT, int CK, bool DGRAD, bool DB = true>
+template <class G, int MF, int MT, int CK, bool DGRAD>
 __global__ void __launch_bounds__(CT_THREADS)
 conv_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                 const float* __restrict__ residual, float* __restrict__ y, Shape s, int xcd_swizzle) {
@@ -661,13 +633,8 @@ conv_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const 
   constexpr int PBUF = PCHP * 4, WBUF = WCHP * 4;                // floats
   constexpr int BUF = PBUF + WBUF;
   constexpr int REDF = WK ? 4 * MT * NT * NREG * 64 : 0;         // cross-wave reduction of the K-split partial sums
-  constexpr int NBUF = DB ? 2 : 1;     // DB = false: one buffer, load -> barrier -> MFMA per chunk; the overlap then comes from the
-                                       // other workgroups of the CU (half the LDS: more of them, and exact occupancy rounds)
-  __shared__ __attribute__((aligned(16))) float lds[(NBUF * BUF > REDF) ? NBUF * BUF : REDF];
+  __shared__ __attribute__((aligned(16))) float lds[(2 * BUF > REDF) ? 2 * BUF : REDF];
 
-#ifdef TG_DIAG_STAMPS
-  const uint64_t st_begin = __builtin_amdgcn_s_memtime();
-#endif
   // TG_DMA_PRIO=1 (off by default): the short serial sections (setup, DMA issue, barrier, epilogue) at wave priority 3, the
   // MFMA blocks at 0.  A young wave otherwise gets the vector issue port only when no older wave has an MFMA waiting
   // (stamps: 8 k cycles of setup for ~200 instructions on the 128^2 layers, 4 k with this) -- but the MFMA phases stretch by
@@ -760,46 +727,14 @@ conv_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const 
   typename Core::acc_t acc[MT][NT];
   Core::zero(acc);
 
-#ifdef TG_DIAG_STAMPS
-  asm volatile("" :: "v"(poff[0]), "v"(woff[0]), "v"(lane_b[0]), "v"(lane_a));
-  const uint64_t st_setup = __builtin_amdgcn_s_memtime();
-#endif
-  if (DB) issue(0, lds);
+  issue(0, lds);
   int buf = 0;
-#ifdef TG_DIAG_STAMPS
-  const uint64_t st_c0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-  uint64_t st_wait = 0, st_bar = 0, st_issue = 0, st_mfma = 0, st_prev = 0, st_last = 0;
-#endif
   for (int c0 = 0; c0 < s.Cin; c0 += CK) {
-    if constexpr (!DB) {
-      __syncthreads();                                         // everybody is done reading the previous chunk
-      issue(c0, lds);
-    }
-#ifdef TG_DIAG_STAMPS
-    const uint64_t ph0 = __builtin_amdgcn_s_memtime();
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's DMAs of chunk c0 have landed ...
-#ifdef TG_DIAG_STAMPS
-    const uint64_t ph1 = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();                                           // ... and everybody's; everybody is done reading the other buffer
-#ifdef TG_DIAG_STAMPS
-    const uint64_t ph2 = __builtin_amdgcn_s_memtime();
-#endif
-    if constexpr (DB) {
-      if (c0 + CK < s.Cin) issue(c0 + CK, lds + (buf ^ 1) * BUF);
-    }
-#ifdef TG_DIAG_STAMPS
-    const uint64_t ph3 = __builtin_amdgcn_s_memtime();
-    st_wait += ph1 - ph0; st_bar += ph2 - ph1; st_issue += ph3 - ph2; st_last = ph3;
-    if (c0 > 0) st_mfma += ph0 - st_prev;
-    st_prev = ph3;
-#endif
+    if (c0 + CK < s.Cin) issue(c0 + CK, lds + (buf ^ 1) * BUF);
     const float* pl = lds + buf * BUF;
     const float* wl = pl + PBUF;
-#ifdef TG_DIAG_STAMPS
-    if (xcd_swizzle & 4) { buf ^= 1; continue; }               // TG_DMA_DIAG=4 (stage isolation, wrong results): no MFMAs
-#endif
     if (prio) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
     for (int gi = 0; gi < NG / (WK ? 4 : 1); ++gi) {
@@ -825,20 +760,8 @@ conv_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const 
       }
     }
     if (prio) __builtin_amdgcn_s_setprio(3);
-    if (DB) buf ^= 1;
+    buf ^= 1;
   }
-#ifdef TG_DIAG_STAMPS
-  {   // diagnostic build only (make diag): shader clock held over the main loop = d(memtime) / d(memrealtime) x 100 MHz
-    const uint64_t st_c1 = __builtin_amdgcn_s_memtime(), st_r1 = __builtin_amdgcn_s_memrealtime();
-    const int slot = blockIdx.y * gridDim.x + blockIdx.x;
-    if (threadIdx.x == 0 && slot < TG_DIAG_SLOTS) { tg_diag_stamps[2 * slot] = st_c1 - st_c0; tg_diag_stamps[2 * slot + 1] = st_r1 - st_r0; }
-    st_mfma += st_c1 - st_last;                                 // per wave: cycles in (vmcnt wait, barrier, DMA issue, MFMA phase)
-    if (lane == 0 && slot < TG_DIAG_SLOTS) {
-      unsigned long long* ph = tg_diag_phases + (slot * 4 + wave) * 4;
-      ph[0] = st_wait; ph[1] = st_bar; ph[2] = st_issue; ph[3] = st_mfma;
-    }
-  }
-#endif
   if constexpr (WK) {
     // sum the four waves' partial accumulators through LDS (fixed order), as conv_fwd_kernel does
     __syncthreads();
@@ -861,22 +784,7 @@ conv_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const 
           acc[m][n][r] = (red[e] + red[PW_ + e]) + (red[2 * PW_ + e] + red[3 * PW_ + e]);
         }
   }
-#ifdef TG_DIAG_STAMPS
-  if ((xcd_swizzle & 2) && acc[0][0][0] != 12345.678f) return;   // TG_DMA_DIAG=2 (stage isolation, wrong results): no epilogue
-#endif
   Core::epilogue(acc, bias, residual, y, s, tc, co0, pix0, j, h, wave);
-#ifdef TG_DIAG_STAMPS
-  {   // workgroup life: entry -> loop, loop -> stores issued, ... -> stores acknowledged
-    const uint64_t e0 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint64_t e1 = __builtin_amdgcn_s_memtime();
-    const int slot = blockIdx.y * gridDim.x + blockIdx.x;
-    if (lane == 0 && slot < TG_DIAG_SLOTS) {
-      unsigned long long* ph = tg_diag_life + (slot * 4 + wave) * 4;
-      ph[0] = st_c0 - st_begin; ph[1] = e0 - st_c0; ph[2] = e1 - e0; ph[3] = st_setup - st_begin;
-    }
-  }
-#endif
 }
 
 // =========================================================================== 1x1, few channels: direct kernel
@@ -1269,11 +1177,10 @@ conv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gy, flo
 // tile go global -> LDS by buffer_load ... lds, nothing passes through VGPRs, no per-element address / bounds code.
 // Same work split (split, co tile, ci chunk), same accumulation order and the same partial-sum layout as
 // conv_wgrad_kernel, so the two are bit-identical and share the plan, the workspace and the reduce kernels.
-// DB: two LDS buffers, the next pixel tile's DMA flies under this tile's MFMAs (one barrier per tile); used where a
-// workgroup walks several tiles and few workgroups share a CU.  The bias gradient is the sum of the A fragments
-// (every gy value of the tile passes through them exactly once).
+// One LDS buffer: load -> barrier -> MFMA per pixel tile; the overlap comes from the other workgroups of the CU.
+// The bias gradient is the sum of the A fragments (every gy value of the tile passes through them exactly once).
 constexpr int WGD_GYQ = 65;                     // chunks per gy row: 256 pixels + one pad chunk (== WG_GYS / 4)
-template <class G, int MTW, int CKW, bool DB>
+template <class G, int MTW, int CKW>
 __global__ void __launch_bounds__(CT_THREADS)
 conv_wgrad_dma_kernel(const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ part,
                       float* __restrict__ bias_part /*nullable: [S][Cout]*/, Shape s, int ntiles, int S) {
@@ -1285,7 +1192,7 @@ conv_wgrad_dma_kernel(const float* __restrict__ x, const float* __restrict__ gy,
   constexpr int NVP = (PCHP + CT_THREADS - 1) / CT_THREADS, NVG = (GCHP + CT_THREADS - 1) / CT_THREADS;
   constexpr int PBUF = PCHP * 4, BUF = PBUF + GCHP * 4;
   constexpr int RED = 4 * MTW * NT * 4 * 64 + 4 * CT;
-  constexpr int LDSF = ((DB ? 2 : 1) * BUF > RED) ? (DB ? 2 : 1) * BUF : RED;
+  constexpr int LDSF = (BUF > RED) ? BUF : RED;
   __shared__ __attribute__((aligned(16))) float lds[LDSF];
 
   const int lane = threadIdx.x & 63, wave = wave_index();
@@ -1371,24 +1278,12 @@ conv_wgrad_dma_kernel(const float* __restrict__ x, const float* __restrict__ gy,
     if (s.prio) __builtin_amdgcn_s_setprio(3);
   };
 
-  if constexpr (DB) {
-    if (split < ntiles) issue(split, lds);
-    int buf = 0;
-    for (int t = split; t < ntiles; t += S) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (t + S < ntiles) issue(t + S, lds + (buf ^ 1) * BUF);
-      compute(lds + buf * BUF);
-      buf ^= 1;
-    }
-  } else {
-    for (int t = split; t < ntiles; t += S) {
-      __syncthreads();                          // everybody is done reading the previous tile
-      issue(t, lds);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      compute(lds);
-    }
+  for (int t = split; t < ntiles; t += S) {
+    __syncthreads();                            // everybody is done reading the previous tile
+    issue(t, lds);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    compute(lds);
   }
 
   // cross-wave reduction through LDS (fixed order), one partial per workgroup -- as conv_wgrad_kernel
@@ -1530,9 +1425,8 @@ conv1x1_wgrad_stream_kernel(const float* __restrict__ x, ChanSegs gys, float* __
   }
 }
 
-static int conv1x1_mode();
 static inline bool conv1x1_wgrad_stream_ok(const float* x, const float* gy, const Shape& s) {
-  return conv1x1_mode() != 0 && (s.H * s.W) % 16 == 0 && tg_aligned16(x) && tg_aligned16(gy);
+  return (s.H * s.W) % 16 == 0 && tg_aligned16(x) && tg_aligned16(gy);
 }
 static int launch_conv1x1_wgrad_segs(const float* x, ChanSegs gy, float* part, float* bias_part, Shape s, int S, hipStream_t st) {
   const int HW = s.H * s.W;
@@ -2029,7 +1923,7 @@ template <class G> struct DPatch2x {            // high-resolution windows of a 
 };
 
 // WK (64-pixel tiles): the four waves share the pixels, wave w takes k-group w of every 16-channel chunk.
-template <class G, bool WK, bool DB = true>
+template <class G, bool WK>
 __global__ void __launch_bounds__(CT_THREADS)
 conv_upT_dma_kernel(const float* __restrict__ gy, const float* __restrict__ w4t, const float* __restrict__ bias,
                     const float* __restrict__ residual, float* __restrict__ ga, Shape s /*Cin = gy channels, Cout = ga channels,
@@ -2042,8 +1936,8 @@ conv_upT_dma_kernel(const float* __restrict__ gy, const float* __restrict__ w4t,
   constexpr int PCHP = dma_pad(PCH), WCHP = dma_pad(WCH);        // regions of whole wave pieces (see dma_pad)
   constexpr int NVP = (PCHP + CT_THREADS - 1) / CT_THREADS, NVW = (WCHP + CT_THREADS - 1) / CT_THREADS;
   constexpr int PBUF = PCHP * 4, BUF = PBUF + WCHP * 4;
-  constexpr int REDF = WK ? 4 * NT * 4 * 64 : 0, NBUF = DB ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) float lds[(NBUF * BUF > REDF) ? NBUF * BUF : REDF];
+  constexpr int REDF = WK ? 4 * NT * 4 * 64 : 0;
+  __shared__ __attribute__((aligned(16))) float lds[(2 * BUF > REDF) ? 2 * BUF : REDF];
   const int lane = threadIdx.x & 63, wave = wave_index();
   if (s.prio) __builtin_amdgcn_s_setprio(3);
   const int j = lane & 15, h = lane >> 4;
@@ -2106,18 +2000,12 @@ conv_upT_dma_kernel(const float* __restrict__ gy, const float* __restrict__ w4t,
   typename Core::acc_t acc[1][NT];
   Core::zero(acc);
 
-  if (DB) issue(0, lds);
+  issue(0, lds);
   int buf = 0;
   for (int c0 = 0; c0 < s.Cin; c0 += CK) {
-    if constexpr (!DB) {
-      __syncthreads();
-      issue(c0, lds);
-    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (DB) {
-      if (c0 + CK < s.Cin) issue(c0 + CK, lds + (buf ^ 1) * BUF);
-    }
+    if (c0 + CK < s.Cin) issue(c0 + CK, lds + (buf ^ 1) * BUF);
     const float* pl = lds + buf * BUF;
     const float* wl = pl + PBUF;
     if (s.prio) __builtin_amdgcn_s_setprio(0);
@@ -2129,7 +2017,7 @@ conv_upT_dma_kernel(const float* __restrict__ gy, const float* __restrict__ w4t,
         acc[0][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, pl[lane_b[n] + (t >> 2) * P::PWS + (t & 3)], acc[0][n], 0, 0, 0);
     }
     if (s.prio) __builtin_amdgcn_s_setprio(3);
-    if (DB) buf ^= 1;
+    buf ^= 1;
   }
   if constexpr (WK) {
     __syncthreads();
@@ -2151,7 +2039,7 @@ conv_upT_dma_kernel(const float* __restrict__ gy, const float* __restrict__ w4t,
   Core::epilogue(acc, bias, residual, ga, s, tc, co0, pix0, j, h, wave);
 }
 
-template <class G, bool WK, bool DB = true>
+template <class G, bool WK>
 __global__ void __launch_bounds__(CT_THREADS)
 conv_upfwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias,
                       const float* __restrict__ residual, float* __restrict__ y, Shape s, int xcd_swizzle) {
@@ -2162,8 +2050,8 @@ conv_upfwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
   constexpr int PCHP = dma_pad(PCH), WCHP = dma_pad(WCH);        // regions of whole wave pieces (see dma_pad)
   constexpr int NVP = (PCHP + CT_THREADS - 1) / CT_THREADS, NVW = (WCHP + CT_THREADS - 1) / CT_THREADS;
   constexpr int PBUF = PCHP * 4, BUF = PBUF + WCHP * 4;
-  constexpr int REDF = WK ? 4 * 2 * NT * 4 * 64 : 0, NBUF = DB ? 2 : 1;
-  __shared__ __attribute__((aligned(16))) float lds[(NBUF * BUF > REDF) ? NBUF * BUF : REDF];
+  constexpr int REDF = WK ? 4 * 2 * NT * 4 * 64 : 0;
+  __shared__ __attribute__((aligned(16))) float lds[(2 * BUF > REDF) ? 2 * BUF : REDF];
   const int lane = threadIdx.x & 63, wave = wave_index();
   if (s.prio) __builtin_amdgcn_s_setprio(3);
   const int j = lane & 15, h = lane >> 4;
@@ -2230,18 +2118,12 @@ conv_upfwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[ph][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  if (DB) issue(0, lds);
+  issue(0, lds);
   int buf = 0;
   for (int c0 = 0; c0 < s.Cin; c0 += CK) {
-    if constexpr (!DB) {
-      __syncthreads();
-      issue(c0, lds);
-    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (DB) {
-      if (c0 + CK < s.Cin) issue(c0 + CK, lds + (buf ^ 1) * BUF);
-    }
+    if (c0 + CK < s.Cin) issue(c0 + CK, lds + (buf ^ 1) * BUF);
     const float* pl = lds + buf * BUF;
     const float* wl = pl + PBUF;
     if (s.prio) __builtin_amdgcn_s_setprio(0);
@@ -2269,7 +2151,7 @@ conv_upfwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
         }
     }
     if (s.prio) __builtin_amdgcn_s_setprio(3);
-    if (DB) buf ^= 1;
+    buf ^= 1;
   }
   if constexpr (WK) {
     float* red = lds;
@@ -2793,7 +2675,6 @@ static inline int64_t s2_min_wgs(GeoId g) { return g == GEO_8 ? 128 : 256; }
 // stride-2 transpose form: 8x8 planes that give fewer than 256 four-image tiles run as single-image K-split tiles
 static bool s2_dma_ok(const void* x, const void* w, const Shape& s, int hi_channels);
 static int dma_prio();
-static bool s2_single_buffer();
 
 static int wino_mode();
 // AvgPool2d(2) o conv3x3 in its 9-frequency form (conv_poolwino_dma_kernel, wino.h) -> true when it took the launch
@@ -2835,12 +2716,6 @@ static void launch_upT(GeoId g, const float* x, const float* w4, const float* bi
     }
     const int t = geo_tiles(g, s.B, s.H, s.W);
     dim3 grid(t, cot);
-    if (s2_single_buffer()) {
-      if (g == GEO_8) conv_upT_dma_kernel<G8, false, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
-      else if (g == GEO_16) conv_upT_dma_kernel<G16, false, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
-      else conv_upT_dma_kernel<GX, false, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
-      return;
-    }
     if (g == GEO_8) conv_upT_dma_kernel<G8, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
     else if (g == GEO_16) conv_upT_dma_kernel<G16, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
     else conv_upT_dma_kernel<GX, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
@@ -2868,12 +2743,6 @@ static void launch_upfwd(GeoId g, const float* x, const float* wp, const float* 
     }
     const int t = geo_tiles(g, s.B, s.H, s.W);
     dim3 grid(t, cot);
-    if (s2_single_buffer()) {
-      if (g == GEO_8) conv_upfwd_dma_kernel<G8, false, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
-      else if (g == GEO_16) conv_upfwd_dma_kernel<G16, false, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
-      else conv_upfwd_dma_kernel<GX, false, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
-      return;
-    }
     if (g == GEO_8) conv_upfwd_dma_kernel<G8, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
     else if (g == GEO_16) conv_upfwd_dma_kernel<G16, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
     else conv_upfwd_dma_kernel<GX, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
@@ -2924,58 +2793,39 @@ int launch_fwd_geo(const float* x, const float* w, const float* bias, const floa
   return tg_launch_status();
 }
 
-// ---- LDS-DMA kernel dispatch.  Tuning knobs are read once from the environment (development only; the defaults are the
-// measured best): TG_CONV_DMA=0 disables the kernel, TG_DMA_TILE=256|512 and TG_DMA_CK=4|8 force a tile / chunk size.
-struct DmaKnobs { int enable, tile, ck, ksplit, wgrad, wgrad_db, s2, db, diag, prio; };
-static const DmaKnobs& dma_knobs() {
-  static const DmaKnobs k = [] {
-    DmaKnobs d{1, 0, 0, 1, 1, 0, 1, 1, 0, 0};
-    if (const char* e = getenv("TG_DMA_PRIO")) d.prio = atoi(e);
-#ifdef TG_DIAG_STAMPS
-    if (const char* e = getenv("TG_DMA_DIAG")) d.diag = atoi(e) & 6;       // stage isolation: the diagnostic build only
-#endif
-    if (const char* e = getenv("TG_DMA_DB")) d.db = atoi(e);
-    if (const char* e = getenv("TG_DMA_S2")) d.s2 = atoi(e);
-    if (const char* e = getenv("TG_DMA_WGRAD")) d.wgrad = atoi(e);
-    if (const char* e = getenv("TG_DMA_WGRAD_DB")) d.wgrad_db = atoi(e);
-    if (const char* e = getenv("TG_DMA_KSPLIT")) d.ksplit = atoi(e);
-    if (const char* e = getenv("TG_CONV_DMA")) d.enable = atoi(e);
-    if (const char* e = getenv("TG_DMA_TILE")) d.tile = atoi(e);
-    if (const char* e = getenv("TG_DMA_CK")) d.ck = atoi(e);
-    return d;
-  }();
-  return k;
+// ---- LDS-DMA kernel dispatch.  Two switches, read once from the environment: TG_CONV_DMA=0 sends every launch to the
+// register-staged kernels (the tests use it to reach them at small shapes), TG_DMA_PRIO=1 see conv_dma_kernel.
+static bool dma_enabled() {
+  static const bool v = [] { const char* e = getenv("TG_CONV_DMA"); return !e || atoi(e) != 0; }();
+  return v;
+}
+static int dma_prio() {
+  static const int v = [] { const char* e = getenv("TG_DMA_PRIO"); return e ? atoi(e) : 0; }();
+  return v;
 }
 
 // stride-2 kernels: whole 16-byte chunks (the callers checked plane / filter alignment), channel counts that keep filter rows
 // 16-byte aligned (x 16 or x 4 floats per channel pair: always), 32-bit buffer offsets; hi_channels > 0: the input is the
 // high-resolution tensor (4x the plane)
 static bool s2_dma_ok(const void* x, const void* w, const Shape& s, int hi_channels) {
-  const DmaKnobs& k = dma_knobs();
-  if (!k.enable || !k.s2) return false;
+  if (!dma_enabled()) return false;
   const int64_t plane = (int64_t)s.H * s.W * (hi_channels ? 4 : 1);
   if ((int64_t)s.B * s.Cin * plane * 4 >= (1ll << 31) || (int64_t)s.Cin * s.Cout * 64 * 4 >= (1ll << 31)) return false;
   return s.W % 4 == 0 || hi_channels;        // low-resolution rows of whole chunks (high-resolution rows: 2 W, the caller's vx)
 }
 
-static bool s2_single_buffer() { return dma_knobs().db == 0; }
-static int dma_prio() { return dma_knobs().prio; }
-
 template <class G, int CK, bool DGRAD>
 static bool launch_dma_geo(const float* x, const float* w, const float* bias, const float* residual, float* y, Shape s, hipStream_t st) {
   const int64_t tiles = num_tiles<G>(s.B, s.H, s.W);
-  const int swz = ((tiles % 8 == 0) ? 1 : 0) | dma_knobs().diag | (dma_knobs().prio ? 32 : 0);
+  const int swz = ((tiles % 8 == 0) ? 1 : 0) | (dma_prio() ? 32 : 0);
   const bool use32 = (s.Cout % 32 == 0) || s.Cout > 48;
   // output-channel tile: as wide as the grid allows (one workgroup per CU at the very least)
-  const bool sb = dma_knobs().db == 0;
   if (use32 && s.Cout > 32 && tiles * ((s.Cout + 63) / 64) >= 512) {
     conv_dma_kernel<G, 32, 2, CK, DGRAD><<<dim3(tiles, (s.Cout + 63) / 64), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
   } else if (use32 && tiles * ((s.Cout + 31) / 32) >= 256) {
-    if (sb) conv_dma_kernel<G, 32, 1, CK, DGRAD, false><<<dim3(tiles, (s.Cout + 31) / 32), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
-    else conv_dma_kernel<G, 32, 1, CK, DGRAD><<<dim3(tiles, (s.Cout + 31) / 32), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
+    conv_dma_kernel<G, 32, 1, CK, DGRAD><<<dim3(tiles, (s.Cout + 31) / 32), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
   } else if (tiles * ((s.Cout + 15) / 16) >= 192) {
-    if (sb) conv_dma_kernel<G, 16, 1, CK, DGRAD, false><<<dim3(tiles, (s.Cout + 15) / 16), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
-    else conv_dma_kernel<G, 16, 1, CK, DGRAD><<<dim3(tiles, (s.Cout + 15) / 16), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
+    conv_dma_kernel<G, 16, 1, CK, DGRAD><<<dim3(tiles, (s.Cout + 15) / 16), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
   } else {
     return false;                      // too few tiles: the K-split variants of conv_fwd_kernel fill the chip better
   }
@@ -2985,7 +2835,7 @@ static bool launch_dma_geo(const float* x, const float* w, const float* bias, co
 template <class G, bool DGRAD>
 static bool launch_dma_ksplit(const float* x, const float* w, const float* bias, const float* residual, float* y, Shape s, hipStream_t st) {
   const int64_t tiles = num_tiles<G>(s.B, s.H, s.W);
-  const int swz = ((tiles % 8 == 0) ? 1 : 0) | (dma_knobs().prio ? 32 : 0);
+  const int swz = ((tiles % 8 == 0) ? 1 : 0) | (dma_prio() ? 32 : 0);
   // 32-channel tiles only while they still give every CU more than one workgroup: with one (or less) per CU nothing
   // overlaps a workgroup's DMA waits, and twice as many 16-channel workgroups win (batch 64: 128->128 @4^2 15.9 -> 10.6 us,
   // 64->128 @8^2 dgrad 15.5 -> 10.2 us, 128->128 @8^2 16.6 -> 16.0 us; 256->256 @8^2, 512 workgroups, stays on 32)
@@ -3000,21 +2850,18 @@ static bool launch_dma_ksplit(const float* x, const float* w, const float* bias,
 template <bool DGRAD>
 static bool try_launch_dma(const float* x, const float* w, const float* bias, const float* residual, float* y, Shape s, hipStream_t st,
                            int* rc) {
-  const DmaKnobs& k = dma_knobs();
-  if (!k.enable) return false;
+  if (!dma_enabled()) return false;
   if (s.W % 4 != 0 || !tg_aligned16(x) || !tg_aligned16(w) || s.Cin % 4 != 0 || s.Cout % 4 != 0) return false;
   if ((int64_t)s.B * s.Cin * s.H * s.W * 4 >= (1ll << 31) || (int64_t)s.Cin * s.Cout * 36 >= (1ll << 31)) return false;
   // channel chunk: 4 keeps more workgroups resident (17 KB of LDS) and wins on the short-K layers; 8 halves the barriers
-  const bool ck4 = (k.ck == 4) || (k.ck == 0 && s.Cin <= 16);
+  const bool ck4 = s.Cin <= 16;
   bool took = false;
-  if (s.H % 16 == 0 && s.W % 32 == 0 && k.tile == 512) {
-    took = ck4 ? launch_dma_geo<GX2, 4, DGRAD>(x, w, bias, residual, y, s, st) : launch_dma_geo<GX2, 8, DGRAD>(x, w, bias, residual, y, s, st);
-  } else if (s.H % 8 == 0 && s.W % 32 == 0) {
+  if (s.H % 8 == 0 && s.W % 32 == 0) {
     took = ck4 ? launch_dma_geo<GX, 4, DGRAD>(x, w, bias, residual, y, s, st) : launch_dma_geo<GX, 8, DGRAD>(x, w, bias, residual, y, s, st);
   } else if (s.H == 16 && s.W == 16) {
     took = ck4 ? launch_dma_geo<G16, 4, DGRAD>(x, w, bias, residual, y, s, st) : launch_dma_geo<G16, 8, DGRAD>(x, w, bias, residual, y, s, st);
   }
-  if (!took && s.Cin >= 16 && k.ksplit) {
+  if (!took && s.Cin >= 16) {
     // small planes with long K: 64-pixel tiles, the four waves split each 16-channel chunk (one workgroup per CU is the
     // normal case here, so the chunk DMA under the MFMAs is the only overlap there is)
     if (s.H == 8 && s.W == 8) took = launch_dma_ksplit<G8k, DGRAD>(x, w, bias, residual, y, s, st);
@@ -3023,11 +2870,6 @@ static bool try_launch_dma(const float* x, const float* w, const float* bias, co
   }
   if (took) *rc = tg_launch_status();
   return took;
-}
-
-static int conv1x1_mode() {
-  static const int v = [] { const char* e = getenv("TG_CONV_1X1"); return e ? atoi(e) : 1; }();
-  return v;
 }
 
 // ---- Winograd F(2x2, 3x3) dispatch (wino.h).  TG_CONV_WINO=0 disables it, 2 takes every eligible shape (tests), 1 (default)
@@ -3109,9 +2951,8 @@ int launch_fwd(const float* x, const float* w, const float* bias, const float* r
     // 32->16) 43.4 -> 31.7; 16->32 @64^2 15.6 -> 13.3; but 64->32 @64^2 22.3 -> 26.5 and 128->64 @32^2 21.1 -> 28.2: with
     // many input channels a wave's serial chain of k-steps is longer than the tiled kernel's four waves sharing a tile.
     // So: at most 32 input channels, and the few-output-channel VALU kernel keeps its shapes.  (The step as a whole does
-    // not move -- these layers sit at the bandwidth their tensors allow; TG_CONV_1X1 = 0 / 2: never / wherever possible.)
-    const int mode = conv1x1_mode();
-    if (mode != 0 && conv1x1_mfma_ok(x, residual, y, s) && (mode == 2 || (!conv1x1_direct_ok(s) && s.Cin <= 32)))
+    // not move -- these layers sit at the bandwidth their tensors allow.)
+    if (conv1x1_mfma_ok(x, residual, y, s) && !conv1x1_direct_ok(s) && s.Cin <= 32)
       return launch_conv1x1_mfma(x, w, bias, residual, y, s, DGRAD, st);
     if (conv1x1_direct_ok(s)) return launch_conv1x1(x, w, bias, residual, y, s, DGRAD, st);
   }
@@ -3152,34 +2993,26 @@ int launch_wgrad_geo(const float* x, const float* gy, float* part, float* bias_p
   const int vx = plane_vec_ok(x, s.W), vg = plane_vec_ok(gy, s.W);
   if constexpr (KS == 3 && G::NPIX == 256) {
     // LDS-DMA staging: needs whole 16-byte chunks (W % 4, aligned planes) and 32-bit buffer offsets
-    const DmaKnobs& k = dma_knobs();
     const bool small = (int64_t)s.B * (s.Cin > s.Cout ? s.Cin : s.Cout) * s.H * s.W * 4 < (1ll << 31);
     constexpr int CKW = WgCfg<3>::CKW;
     constexpr int buf1 = (dma_pad(CKW * DPatch<G>::CPC) + dma_pad(16 * WGD_GYQ)) * 16, buf2 = (dma_pad(CKW * DPatch<G>::CPC) + dma_pad(32 * WGD_GYQ)) * 16;   // bytes, MTW 1 / 2
-    if (k.enable && k.wgrad && vx && vg && small) {
-      s.prio = k.prio;
-      // (two buffers -- the next tile in flight under this tile's MFMAs -- measured slower at every shape of the 128 px step:
-      // they halve the workgroups per CU; kept behind TG_DMA_WGRAD_DB=1 for wider layers)
-      const bool db = k.wgrad_db == 1 || (k.wgrad_db < 0 && p.tiles >= 2 * p.S && (int64_t)p.S * p.co_tiles * p.ci_chunks <= 600);
+    if (dma_enabled() && vx && vg && small) {
+      s.prio = dma_prio();
+      // (one LDS buffer per workgroup: two -- the next tile in flight under this tile's MFMAs -- measured slower at every
+      // shape of the 128 px step, they halve the workgroups per CU)
       if (s.Cin <= 4 && p.mtw == 1) {
         // the composed from-RGB layer (3 image channels + the bias channel): 36 (ci, tap) columns, not 144
-        conv_wgrad_dma_kernel<G, 1, 4, false><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
+        conv_wgrad_dma_kernel<G, 1, 4><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
         return tg_launch_status();
       }
       if (p.mtw == 2) {
-        if constexpr (2 * buf2 <= 160 * 1024) {
-          if (db) { conv_wgrad_dma_kernel<G, 2, CKW, true><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S); return tg_launch_status(); }
-        }
         if constexpr (buf2 <= 160 * 1024) {
-          conv_wgrad_dma_kernel<G, 2, CKW, false><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
+          conv_wgrad_dma_kernel<G, 2, CKW><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
           return tg_launch_status();
         }
       } else {
-        if constexpr (2 * buf1 <= 160 * 1024) {
-          if (db) { conv_wgrad_dma_kernel<G, 1, CKW, true><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S); return tg_launch_status(); }
-        }
         if constexpr (buf1 <= 160 * 1024) {
-          conv_wgrad_dma_kernel<G, 1, CKW, false><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
+          conv_wgrad_dma_kernel<G, 1, CKW><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
           return tg_launch_status();
         }
       }
@@ -3337,8 +3170,8 @@ static int s2_wgrad_stage1(const float* hi, const float* lo, float* ws, size_t w
   dim3 grid(S, p.lo_tiles, p.hi_chunks);
   float* bias_part = want_bias ? ws + (size_t)S * Clo * Chi * 16 : nullptr;      // [S][Cout]: Cout == Clo (mode 0) or Chi (mode 1)
   const int vh = plane_vec_ok(hi, 2 * W), vl = plane_vec_ok(lo, W);
-  if (vh && vl && dma_knobs().enable && dma_knobs().wgrad && (int64_t)B * (Chi > Clo ? Chi : Clo) * H * W * 16 < (1ll << 31)) {
-    s.prio = dma_knobs().prio;
+  if (vh && vl && dma_enabled() && (int64_t)B * (Chi > Clo ? Chi : Clo) * H * W * 16 < (1ll << 31)) {
+    s.prio = dma_prio();
     TG_S2_DISPATCH(g, conv_wgrad_s2_dma_kernel, hi, lo, ws, s, tiles, S, bias_part, mode);
   } else {
     TG_S2_DISPATCH(g, conv_wgrad_s2_kernel, hi, lo, ws, s, tiles, S, vh, vl, bias_part, mode);

@@ -10,8 +10,6 @@
 // rows / columns / K tails are lanes whose buffer offset fails the bounds check (zeros, no memory touched).
 // Operands are row-major; "TA" reads A^T (the covariance X_c^T X_c).  Epilogue: C = alpha * A B + diag * I
 // (the Newton-Schulz step T = 1.5 I - 0.5 Z Y in one pass).
-#include <cstdlib>
-
 #include "common.h"
 
 namespace {
@@ -195,8 +193,7 @@ int tg_gemm_big(const float* A, const float* Bm, float* C, int M, int N, int K, 
   hipStream_t st = tg_stream(stream);
   // 128 x 128 tiles when they give every CU two workgroups (the second hides the first one's barriers); else 128 x 64
   const int tm = (M + GB_BM - 1) / GB_BM;
-  static const int force = [] { const char* e = getenv("TG_GEMM_BN"); return e ? atoi(e) : 0; }();    // (development knob)
-  const bool wide = force ? force == 128 : (int64_t)tm * ((N + 127) / 128) >= 512;
+  const bool wide = (int64_t)tm * ((N + 127) / 128) >= 512;
   if (wide) {
     const int tiles = tm * ((N + 127) / 128);
     if (transA) gemm_big_kernel<true, 128><<<tiles, GB_T, 0, st>>>(A, Bm, C, M, N, K, lda, ldb, ldc, alpha, diag, bytesA, bytesB);

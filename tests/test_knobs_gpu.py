@@ -1,6 +1,7 @@
-"""The development knobs of the LDS-DMA kernels select other instantiations of the same templates (512-pixel tiles, single buffer,
-4 / 8-channel chunks, wave priorities, the register-staged kernels).  They are not defaults, but they are compiled in: each must
-still give the right numbers (tools/knob_check.py: plain torch on the CPU as the reference, batch 64, NaN-poisoned LDS)."""
+"""The switches of the 3x3 convolution dispatch select other kernels for the same launches (Winograd off / wherever eligible, the
+direct LDS-DMA kernels with wave priorities, the register-staged kernels).  They are not defaults, but they are compiled in and some
+inputs reach those kernels only: each must still give the right numbers (tools/knob_check.py: plain torch on the CPU as the
+reference, batch 64, NaN-poisoned LDS)."""
 import os
 import subprocess
 import sys
@@ -11,9 +12,8 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # The Winograd kernels (TG_CONV_WINO, default 1) take the stride-1 3x3 launches that fill the chip and the >= 32-channel pooled
-# convolutions; the direct kernels behind them -- what every TG_DMA_* knob selects among -- run with TG_CONV_WINO=0.
-_DIRECT = [{'TG_DMA_TILE': '512'}, {'TG_DMA_TILE': '512', 'TG_DMA_CK': '4'}, {'TG_DMA_DB': '0'}, {'TG_DMA_CK': '4'}, {'TG_DMA_CK': '8'},
-           {'TG_DMA_PRIO': '1'}, {'TG_DMA_WGRAD_DB': '1'}, {'TG_DMA_S2': '0'}, {'TG_DMA_WGRAD': '0'}, {'TG_DMA_KSPLIT': '0'}, {'TG_CONV_DMA': '0'}]
+# convolutions; the direct kernels behind them run with TG_CONV_WINO=0.
+_DIRECT = [{'TG_DMA_PRIO': '1'}, {'TG_CONV_DMA': '0'}]
 KNOBS = [{}, {'TG_CONV_WINO': '0'}, {'TG_CONV_WINO': '2'}] + [dict(k, TG_CONV_WINO='0') for k in _DIRECT]
 
 
