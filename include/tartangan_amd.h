@@ -476,6 +476,28 @@ int tg_sn_power_iter(const float* W, float* u, float* v, float* sigma /*nullable
                      int rows, int cols, int n_iter, float eps, void* stream);
 /* out = 1 / x */
 int tg_recip(const float* x, float* out, int64_t n, void* stream);
+/* The same for every layer of a network at once (tg_version 107): ONE power iteration, sigma, the normalised weight and its
+ * backward, in a number of launches that does not depend on the number of layers (4 forward with update, 2 without, 2 backward,
+ * per group of 48 layers).  `items` is a HOST array of n_items x TG_SN_ITEM_FIELDS 64-bit words, read during the call only:
+ *   [0] w_orig  [1] u  [2] v  [3] w_sn  [4] g_sn  [5] g_orig  (device addresses; [4], [5] may be 0 for the forward)
+ *   [6] rows  [7] cols                                          (w_orig, w_sn, g_sn, g_orig: rows x cols row-major)
+ * tg_sn_batch_fwd  update != 0: v = normalize(W^T u, eps), u = normalize(W v, eps) in place (x / max(|x|, eps), as torch);
+ *                  update == 0: u, v are only read.  Either way sigma[i] = u^T W v and w_sn = w_orig / sigma[i].
+ * tg_sn_batch_bwd  g_orig += (g_sn - <g_sn, w_sn> u v^T) / sigma[i]: the gradient of W / sigma(W) with u, v constant, from the
+ *                  sigma a forward call left; clear != 0 leaves g_sn all zeros, clear == 0 leaves it untouched.
+ * workspace: tg_sn_batch_workspace(items, n_items) bytes (0 for a table the calls below refuse), scratch within one call.
+ * Stages are ordered by launch boundaries alone; every sum runs in one fixed order (two calls give the same bits).
+ * Every device pointer may sit at any multiple of 4 bytes: float4 accesses are used where the pointers involved are 16-byte
+ * aligned and cols % 4 == 0, a scalar path otherwise, and both give the same bits.  A layer may appear once per call.
+ * n_items < 1, a null items / sigma / workspace, a zero address among [0..3] (backward: [0..5]), an address that is no multiple
+ * of 4, rows or cols < 1: TG_EINVAL; rows * cols >= 2^31: TG_EUNSUPPORTED; a workspace below the query: TG_EWORKSPACE; nothing
+ * launched or written in any of these cases.                                                                                  */
+#define TG_SN_ITEM_FIELDS 8
+size_t tg_sn_batch_workspace(const tg_host_i64* items /*host*/, int n_items);
+int tg_sn_batch_fwd(const tg_host_i64* items /*host*/, int n_items, float* sigma /*device, n_items floats*/, float* workspace,
+                    size_t workspace_bytes, int update, float eps, void* stream);
+int tg_sn_batch_bwd(const tg_host_i64* items /*host*/, int n_items, const float* sigma, float* workspace, size_t workspace_bytes,
+                    int clear, void* stream);
 
 /* ---------------------------------------------------------------- optimiser / EMA
  * torch.optim.Adam (trainers/cnn.py:84-85), single flat tensor.

@@ -1233,6 +1233,11 @@ def filter_forms_active():
 _KNOWN_FORMS = weakref.WeakKeyDictionary()       # module -> {id(weight): weakref(weight)}; beside the module, not in it (pickling)
 
 
+def _persistent_weight(w):
+    """A filter that is the same tensor from scope to scope: a parameter, or the materialised weight of a spectral-norm layer."""
+    return isinstance(w, torch.nn.Parameter) or (torch.is_tensor(w) and getattr(w, '_tg_sn_leaf', False))
+
+
 def _known_forms(owner):
     known = _KNOWN_FORMS.get(owner)
     if known is None:
@@ -1244,7 +1249,9 @@ def _known_forms(owner):
             if isinstance(m, torch.nn.Sequential) and len(m) >= 2:
                 conv, pool = m[len(m) - 2], m[len(m) - 1]
                 w = getattr(conv, 'weight', None)
-                if (type(pool).__name__ == 'AvgPool2d' and isinstance(w, torch.nn.Parameter) and w.dim() == 4
+                if w is None:
+                    w = getattr(conv, '_sn_leaf', None)          # a spectral-norm layer inside its scope: the materialised weight
+                if (type(pool).__name__ == 'AvgPool2d' and _persistent_weight(w) and w.dim() == 4
                         and tuple(w.shape[2:]) == (3, 3)):
                     known[id(w)] = weakref.ref(w)
     return known
@@ -1284,7 +1291,7 @@ def _poolconv_weights(x_like, w):
     K().poolconv3x3_weights(w.contiguous(), w4, wp, Cout, Cin)
     if cache is not None and w.is_contiguous():
         cache[key] = (w, w._version, w4, wp)
-        if _FilterForms.owner is not None and isinstance(w, torch.nn.Parameter):
+        if _FilterForms.owner is not None and _persistent_weight(w):
             _known_forms(_FilterForms.owner)[id(w)] = weakref.ref(w)
     return w4, wp
 
@@ -2483,6 +2490,186 @@ def spectral_normalize(weight, u, v, training, n_power_iterations=1, eps=1e-12):
     wv = matmul(wmat, v.view(cols, 1)).view(rows)
     sigma = _Dot.apply(u, wv, 1.0)
     return _ScaleDev.apply(_Recip.apply(sigma), weight, 1.0)
+
+
+# --------------------------------------------------------------------------- spectral scopes (the batched route)
+def _al4(n):
+    return (n + 3) // 4 * 4
+
+
+class _SpectralStore:
+    """What a network's spectral-norm layers share on the batched route: one arena of materialised weights ``w_sn``, one of their
+    gradients ``g_sn``, one flat u | v buffer whose views ARE the layers' registered buffers, one sigma vector, one workspace and
+    the host item table of tg_sn_batch_fwd / tg_sn_batch_bwd.  Each ``w_sn`` is a detached LEAF view of its arena with ``.grad``
+    pre-bound to its ``g_sn`` slice: inside ``grads_into_buckets()`` the conv Functions deposit weight gradients straight into
+    ``g_sn`` (``_grad_sink``), and autograd never differentiates the normalisation itself -- ``backward()`` maps ``g_sn`` onto
+    ``weight_orig.grad``, which is exact because that map is linear and u, v, sigma are fixed inside a scope.
+    ``generation`` counts rebuilds (a captured graph holds the addresses of one generation)."""
+
+    def __init__(self):
+        self.generation = -1
+        self.layers = None
+        self.active = False
+
+    def bound(self, layers):
+        """Pointer compares only: are these still the layers, parameters, gradients and buffers the table was built from?"""
+        if self.layers is None or len(layers) != len(self.layers) or any(a is not b for a, b in zip(layers, self.layers)):
+            return False
+        for m, row, (uo, vo) in zip(layers, self.rows, self.uv_offs):
+            g = m.weight_orig.grad
+            if (m.weight_orig.data_ptr() != row[0] or g is None or g.data_ptr() != row[5] or not g.is_contiguous()
+                    or m.weight_u.data_ptr() != row[1] or m.weight_v.data_ptr() != row[2]):
+                return False
+        return True
+
+    def build(self, layers):
+        dev = layers[0].weight_orig.device
+        offs, n, uv_offs, k = [], 0, [], 0
+        for m in layers:
+            offs.append(n)
+            n += _al4(m.weight_orig.numel())
+            rows, cols = m.weight_orig.shape[0], m.weight_orig[0].numel()
+            uv_offs.append((k, k + _al4(rows)))
+            k += _al4(rows) + _al4(cols)
+        self.w_sn = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.g_sn = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.uv = torch.zeros(k, dtype=torch.float32, device=dev)
+        self.sigma = torch.ones(len(layers), dtype=torch.float32, device=dev)
+        self.leaves, self.grad_views, self.rows = [], [], []
+        with torch.no_grad():
+            for m, off, (uo, vo) in zip(layers, offs, uv_offs):
+                p = m.weight_orig
+                rows, cols = p.shape[0], p[0].numel()
+                u, v = self.uv[uo:uo + rows], self.uv[vo:vo + cols]
+                u.copy_(m.weight_u)
+                v.copy_(m.weight_v)
+                m._buffers['weight_u'], m._buffers['weight_v'] = u, v          # same keys, same values: now views of the flat buffer
+                if p.grad is None or not p.grad.is_contiguous():
+                    p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                leaf = self.w_sn[off:off + p.numel()].view(p.shape)
+                gview = self.g_sn[off:off + p.numel()].view(p.shape)
+                leaf.requires_grad_(p.requires_grad)
+                leaf.grad = gview
+                leaf._tg_sn_leaf = True                                     # (filter_forms: as persistent as a parameter)
+                self.leaves.append(leaf)
+                self.grad_views.append(gview)
+                self.rows.append([p.data_ptr(), u.data_ptr(), v.data_ptr(), leaf.data_ptr(), gview.data_ptr(), p.grad.data_ptr(), rows, cols])
+        self.table = torch.tensor(self.rows, dtype=torch.int64)
+        self.nbytes = int(K().sn_batch_workspace(self.table, len(layers)))
+        self.ws = torch.empty(max(1, (self.nbytes + 3) // 4), dtype=torch.float32, device=dev)
+        self.layers, self.uv_offs, self.eps = list(layers), uv_offs, float(layers[0].sn_eps)
+        self.generation += 1
+
+    def materialize(self, update):
+        K().sn_batch_fwd(self.table, len(self.layers), self.sigma, self.ws, self.nbytes, int(bool(update)), self.eps)
+
+    def backward(self):
+        for leaf, gview in zip(self.leaves, self.grad_views):
+            g = leaf.grad
+            if g is not gview and (g is None or g.data_ptr() != gview.data_ptr()):
+                # autograd replaced the pre-bound gradient (a backward with create_graph, or zero_grad(set_to_none)): take it in
+                with torch.no_grad():
+                    if g is None:
+                        gview.zero_()
+                    else:
+                        gview.copy_(g)
+                leaf.grad = gview
+        K().sn_batch_bwd(self.table, len(self.layers), self.sigma, self.ws, self.nbytes, 1)
+
+
+_SPECTRAL_STORES = weakref.WeakKeyDictionary()       # module -> _SpectralStore; beside the module, not in it (pickling, deepcopy)
+_SPECTRAL_LAYERS = weakref.WeakKeyDictionary()       # module -> (key, [layers]): the module walk, cached like optim._param_list
+
+
+def _spectral_layers(module):
+    """The layers of ``module`` that take the batched route: ``SpectralNormConv2d`` with ``n_power_iterations == 1`` (any other
+    count stays on the per-layer route) and one eps (the entry point takes one)."""
+    cached = _SPECTRAL_LAYERS.get(module)
+    key = len(module._modules)
+    if cached is not None and cached[0] == key and cached[2][0] < 64:
+        cached[2][0] += 1
+        return cached[1]
+    layers = [m for m in module.modules() if type(m).__name__ == 'SpectralNormConv2d' and hasattr(m, 'weight_orig')
+              and m.n_power_iterations == 1]
+    layers = [m for m in layers if m.sn_eps == layers[0].sn_eps]
+    _SPECTRAL_LAYERS[module] = (key, layers, [0])
+    return layers
+
+
+def spectral_store(module):
+    """The (built, bound) ``_SpectralStore`` of ``module``, or None when it has no layer for the batched route.  Rebuilt -- a new
+    ``generation`` -- when the layer set, a parameter, its gradient or a u / v buffer is no longer where the item table says
+    (``FusedAdam`` re-homed the parameters, ``module.to()``, a checkpoint loaded by pickling).  Never call it for the first time
+    under stream capture: the trainers build their stores in ``build_models`` and before a capture."""
+    layers = _spectral_layers(module)
+    if not layers:
+        return None
+    store = _SPECTRAL_STORES.get(module)
+    if store is None:
+        store = _SPECTRAL_STORES[module] = _SpectralStore()
+    if not store.bound(layers):
+        if store.active:
+            raise RuntimeError('spectral_scope: the network was re-homed while a scope for it is open')
+        store.build(layers)
+    return store
+
+
+@contextlib.contextmanager
+def spectral_scope(module, update=True):
+    """Scope in which ``module``'s weights do not change (where the trainers open ``filter_forms``): ALL of its spectral-norm layers
+    get ONE power iteration (``update`` and the module in training mode; otherwise sigma comes from the stored u, v), one
+    ``w_sn = weight_orig / sigma`` per layer is materialised, and every forward inside the scope convolves with it -- 4 launches
+    for the whole network (tg_sn_batch_fwd) instead of ~7 per layer and forward.  Gradients w.r.t. ``w_sn`` collect in the
+    store; ``spectral_backward(module)`` maps them onto ``weight_orig.grad`` after the scope's backward passes.  A scope for a
+    module that already has one open, or without such layers, does nothing."""
+    store = spectral_store(module)
+    if store is None or store.active:
+        yield
+        return
+    with torch.no_grad():
+        store.materialize(update and module.training)
+    store.active = True
+    for m, leaf in zip(store.layers, store.leaves):
+        m._sn_leaf = leaf
+    try:
+        yield
+    finally:
+        store.active = False
+        for m in store.layers:
+            m._sn_leaf = None
+
+
+def spectral_backward(module):
+    """``weight_orig.grad += (g_sn - <g_sn, w_sn> u v^T) / sigma`` for all layers of ``module`` in 2 launches (tg_sn_batch_bwd), from
+    the u, v, sigma of the last scope; ``g_sn`` is left zero for the next phase.  Call it after ``backward`` (and after
+    ``deferred_wgrad()`` has exited: its batched reduce lands in ``g_sn`` too), before the gradients are reduced or stepped on."""
+    store = spectral_store(module)
+    if store is not None:
+        store.backward()
+
+
+def spectral_leaves(module):
+    """The materialised-weight leaves of ``module`` that currently want a gradient (for ``backward(inputs=...)``)."""
+    store = spectral_store(module)
+    return [] if store is None else [leaf for leaf in store.leaves if leaf.requires_grad]
+
+
+def spectral_original_ids(module):
+    """ids of the ``weight_orig`` parameters whose gradient arrives through ``spectral_backward`` (not through autograd)."""
+    store = spectral_store(module)
+    return set() if store is None else {id(m.weight_orig) for m in store.layers}
+
+
+def spectral_sync_uv(target, source):
+    """Copy ``source``'s u | v buffers into ``target``'s (same architecture): ONE copy of the flat buffer.  An EMA moves parameters
+    only, so a target network's u and v would otherwise stay at their random initial values."""
+    t, s = spectral_store(target), spectral_store(source)
+    if t is None or s is None:
+        return
+    if t.uv.numel() != s.uv.numel():
+        raise RuntimeError('spectral_sync_uv: the two networks do not hold the same spectral-norm layers')
+    with torch.no_grad():
+        t.uv.copy_(s.uv)
 
 
 class _LReluBwd(Function):

@@ -15,7 +15,7 @@ from torch import nn
 
 from ... import functional as TF
 from ..iqn import IQN, CosineQuantileEmbedding, iqn_loss
-from ..layers import AvgPool2d, BatchNorm2d, Conv2d, LeakyReLU, Linear, Tanh, interpolate, run_layers
+from ..layers import AvgPool2d, BatchNorm2d, Conv2d, LeakyReLU, Linear, Tanh, conv_weight, fusable_conv, interpolate, run_layers
 
 _lrelu = functools.partial(LeakyReLU, 0.2)
 _half = functools.partial(interpolate, scale_factor=0.5, mode='bilinear', align_corners=True)
@@ -80,8 +80,8 @@ class ResidualDiscriminatorBlock(nn.Module):
         default resampling."""
         mods = list(self.convs)
         rc = list(getattr(rgb, 'convs', []))
-        return (isinstance(rgb, DiscriminatorInput) and len(rc) == 1 and type(rc[0]) is Conv2d and rc[0].kernel_size == (1, 1)
-                and rc[0].bias is not None and len(mods) > 1 and type(mods[0]) is Conv2d and mods[0].kernel_size == (3, 3)
+        return (isinstance(rgb, DiscriminatorInput) and len(rc) == 1 and fusable_conv(rc[0]) and rc[0].kernel_size == (1, 1)
+                and rc[0].bias is not None and len(mods) > 1 and fusable_conv(mods[0]) and mods[0].kernel_size == (3, 3)
                 and self.project_input is None and _is_half(self.interpolate))
 
     def forward_from_rgb(self, img, rgb):
@@ -91,14 +91,18 @@ class ResidualDiscriminatorBlock(nn.Module):
         One 4->C 3x3 convolution replaces a 3->C 1x1 and a C->C 3x3 one (C = 16 at 128 px: 4x fewer multiply-adds at
         the full resolution), and the shortcut's bilinear-1/2 runs on the 3-channel image (it commutes with the 1x1)."""
         rgb_conv, conv1 = rgb.convs[0], self.convs[0]
-        C, Cimg = rgb_conv.weight.shape[:2]
-        Cout = conv1.weight.shape[0]
-        wc = TF.compose_rgb_filter(rgb_conv.weight, rgb_conv.bias, conv1.weight)                      # one launch (and one backwards)
+        w1, w3 = conv_weight(rgb_conv), conv_weight(conv1)           # (spectral-norm layers: their effective weights, once per forward)
+        C, Cimg = w1.shape[:2]
+        Cout = w3.shape[0]
+        wc = TF.compose_rgb_filter(w1, rgb_conv.bias, w3)                                             # one launch (and one backwards)
         img_a = img_b = img
         if img.requires_grad and torch.is_grad_enabled():
             img_a, img_b = TF.fork(img, 2)         # two consumers (R1 differentiates w.r.t. the images): one fan-in kernel
         h = TF.conv2d(TF.copy_channels(img_a, Cimg + 1, 1.0), wc.view(Cout, Cimg + 1, 3, 3), conv1.bias)     # [img, 1] in one pass
-        shortcut = run_layers(rgb.convs, self.interpolate(img_b))
+        if type(rgb_conv) is Conv2d:
+            shortcut = run_layers(rgb.convs, self.interpolate(img_b))
+        else:
+            shortcut = TF.conv2d(self.interpolate(img_b), w1, rgb_conv.bias)
         return run_layers(self.convs[1:], h, residual=shortcut)
 
 

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from ... import functional as TF
-from ..layers import BatchNorm2d, Conv2d, LeakyReLU, Linear, Tanh, run_layers
+from ..layers import BatchNorm2d, Conv2d, LeakyReLU, Linear, Tanh, conv_weight, fusable_conv, run_layers
 
 _lrelu = functools.partial(LeakyReLU, 0.2)
 
@@ -43,7 +43,7 @@ class ResidualGeneratorBlock(nn.Module):
             return run_layers(self.convs, x, residual=shortcut)      # x + h, the add fused into the last conv
         mods = list(self.convs)
         low_res_norm = (len(mods) > 2 and isinstance(mods[0], BatchNorm2d) and isinstance(mods[1], LeakyReLU))
-        if low_res_norm and (self.project_input is None or all(type(m) is Conv2d for m in self.project_input)):
+        if low_res_norm and (self.project_input is None or all(fusable_conv(m) for m in self.project_input)):
             # Everything between the block input and the first 3x3 conv commutes with nearest-neighbour upsampling:
             # BatchNorm statistics of an upsampled tensor are those of its source (each element 4 times), LeakyReLU is
             # elementwise, and the 1x1 projection acts per pixel.  So norm + activation and the projection run at
@@ -59,8 +59,9 @@ class ResidualGeneratorBlock(nn.Module):
             # (tg_conv2d_fwd_up2res), no high-resolution copy is written or read
             shortcut = xs if self.project_input is None else run_layers(self.project_input, xs)
             conv = mods[2]
-            if type(conv) is Conv2d and conv.kernel_size == (3, 3) and len(mods) > 3 and TF.upconv3x3_pays(a, conv.weight):
-                return run_layers(self.convs[3:], TF.upconv3x3(a, conv.weight, conv.bias), residual=shortcut, residual_up=True)
+            if (fusable_conv(conv) and conv.kernel_size == (3, 3) and len(mods) > 3
+                    and TF.upconv3x3_pays(a, conv.weight if type(conv) is Conv2d else conv.weight_orig)):
+                return run_layers(self.convs[3:], TF.upconv3x3(a, conv_weight(conv), conv.bias), residual=shortcut, residual_up=True)
             return run_layers(self.convs[2:], TF.upsample_nearest2x(a), residual=shortcut, residual_up=True)
         if not TF._is_pair(x) and x.dim() == 3:          # (B, C, L), the text trainer: the two uses of up(x) meet in autograd
             xs = xu = TF.upsample_nearest2x_1d(x)

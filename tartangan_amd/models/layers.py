@@ -35,7 +35,11 @@ class Conv2d(nn.Conv2d):
 class SpectralNormConv2d(Conv2d):
     """``conv_factory`` with spectral normalisation (what ``torch.nn.utils.spectral_norm(nn.Conv2d(...))`` gives):
     parameters ``weight_orig`` / ``bias``, buffers ``weight_u`` / ``weight_v``, one power iteration per training
-    forward, ``weight = weight_orig / sigma``.  Off by default: the reference's trainers never apply it."""
+    forward, ``weight = weight_orig / sigma``.  Off by default: the reference's trainers never apply it.
+
+    Inside a ``functional.spectral_scope`` opened for a network that holds the layer (the trainers' ``--spectral-norm``), the
+    weight is the one the scope materialised for all of the network's layers at once: no iteration per forward, the same
+    weight for every forward of the scope, its gradient mapped back by ``functional.spectral_backward``."""
 
     def __init__(self, *args, n_power_iterations=1, eps=1e-12, **kw):
         super().__init__(*args, **kw)
@@ -49,10 +53,59 @@ class SpectralNormConv2d(Conv2d):
         self.register_buffer('weight_v', v)
         self.n_power_iterations, self.sn_eps = n_power_iterations, eps
 
+    _sn_leaf = None          # set by an open functional.spectral_scope: the materialised weight_orig / sigma (a leaf)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_sn_leaf', None)            # a view of a scope's arena does not travel with a checkpoint
+        return state
+
+    def effective_weight(self):
+        """The filter this forward convolves with.  Outside a spectral scope: one power iteration now (training mode), then
+        ``weight_orig / sigma`` differentiable w.r.t. ``weight_orig`` -- call it ONCE per forward."""
+        leaf = self._sn_leaf
+        if leaf is not None:
+            if leaf.requires_grad != self.weight_orig.requires_grad:        # (toggle_grad only reaches parameters)
+                leaf.requires_grad_(self.weight_orig.requires_grad)
+            return leaf
+        return TF.spectral_normalize(self.weight_orig, self.weight_u, self.weight_v, self.training,
+                                     self.n_power_iterations, self.sn_eps)
+
     def forward(self, x):
-        w = TF.spectral_normalize(self.weight_orig, self.weight_u, self.weight_v, self.training,
-                                  self.n_power_iterations, self.sn_eps)
-        return TF.conv2d(x, w, self.bias)
+        return TF.conv2d(x, self.effective_weight(), self.bias)
+
+
+def fusable_conv(m):
+    """A convolution layer whose filter ``run_layers`` and the blocks may hand to a fused route themselves."""
+    return type(m) is Conv2d or type(m) is SpectralNormConv2d
+
+
+def conv_weight(m):
+    """The filter of a ``fusable_conv`` layer (a spectral-norm layer: see ``effective_weight``, once per forward)."""
+    return m.weight if type(m) is Conv2d else m.effective_weight()
+
+
+def strip_spectral_norm(state_dict):
+    """A plain state_dict from one with spectral-norm layers (the role of ``remove_all_spectral_norm`` in the reference's
+    prep4web.py:33-51): every ``X.weight_orig`` / ``X.weight_u`` / ``X.weight_v`` triple becomes ``X.weight = weight_orig /
+    sigma`` with ``sigma = u^T W v`` from the stored u and v (no iteration: what the layer computes in eval mode).  Other keys
+    pass through; the order of the keys is kept.  A stock ``Generator`` / ``Discriminator`` loads the result."""
+    out = type(state_dict)()
+    for key, val in state_dict.items():
+        if key.endswith('weight_u') or key.endswith('weight_v'):
+            continue
+        if key.endswith('weight_orig'):
+            stem = key[:-len('_orig')]
+            u, v = state_dict[stem + '_u'].double(), state_dict[stem + '_v'].double()
+            w = val.detach().double()
+            sigma = torch.dot(u, torch.mv(w.reshape(w.shape[0], -1), v))
+            out[stem] = (w / sigma).to(val.dtype)
+        else:
+            out[key] = val
+    meta = getattr(state_dict, '_metadata', None)
+    if meta is not None:
+        out._metadata = meta
+    return out
 
 
 class Linear(nn.Linear):
@@ -175,7 +228,7 @@ def run_layers(seq, x, residual=None, residual_up=False):
     ``residual_up``: the shortcut is given at half the resolution of the result (generator blocks); a final 3x3 Conv2d adds it
     upsampled on the fly, anything else gets it upsampled first."""
     mods = list(seq)
-    if residual_up and not (mods and type(mods[-1]) is Conv2d and mods[-1].kernel_size == (3, 3)):
+    if residual_up and not (mods and fusable_conv(mods[-1]) and mods[-1].kernel_size == (3, 3)):
         residual, residual_up = TF.upsample_nearest2x(residual), False
     i = 0
     while i < len(mods):
@@ -190,15 +243,15 @@ def run_layers(seq, x, residual=None, residual_up=False):
             x = m.forward_act(x, mods[i + 1].negative_slope)
             i += 2
             continue
-        if (i == len(mods) - 2 and type(m) is Conv2d and type(mods[i + 1]) is AvgPool2d and m.kernel_size == (3, 3)
-                and x.dim() == 4 and TF.pool_conv3x3_supported(x, m.weight)):
+        if (i == len(mods) - 2 and fusable_conv(m) and type(mods[i + 1]) is AvgPool2d and m.kernel_size == (3, 3)
+                and x.dim() == 4 and TF.pool_conv3x3_supported(x, m.weight if type(m) is Conv2d else m.weight_orig)):
             # conv3x3 -> AvgPool2d(2) [+ shortcut]: one 4x4-tap stride-2 convolution (2.25x fewer FLOPs, no full-resolution
             # conv output, no pool pass)
-            x, residual = TF.pool_conv3x3(x, m.weight, m.bias, residual), None
+            x, residual = TF.pool_conv3x3(x, conv_weight(m), m.bias, residual), None
             i += 2
             continue
-        if last and residual is not None and type(m) is Conv2d:
-            x, residual = TF.conv2d(x, m.weight, m.bias, residual, residual_up), None
+        if last and residual is not None and fusable_conv(m):
+            x, residual = TF.conv2d(x, conv_weight(m), m.bias, residual, residual_up), None
         elif last and residual is not None and type(m) is AvgPool2d:
             x, residual = TF.avg_pool2(x, residual), None
         else:

@@ -7,6 +7,7 @@
 order), Adam(0, .999), G phase, EMA of G -- with identical op order, RNG
 consumption order, BatchNorm mode and label layout.
 """
+import contextlib
 import functools
 
 import numpy as np
@@ -16,10 +17,10 @@ from torch import nn
 from .. import backend as _be
 from .. import functional as TF
 from ..models.blocks import (
-    DiscriminatorOutput, GeneratorInputMLP, GeneratorOutput, ResidualDiscriminatorBlock,
+    DiscriminatorInput, DiscriminatorOutput, GeneratorInputMLP, GeneratorOutput, ResidualDiscriminatorBlock,
     ResidualGeneratorBlock, TiledZGeneratorInput,
 )
-from ..models.layers import ELU, SELU, BatchNorm2d, LeakyReLU
+from ..models.layers import ELU, SELU, BatchNorm2d, LeakyReLU, SpectralNormConv2d
 from ..models.losses import gradient_penalty
 from ..models.pluggan import GAN_CONFIGS, Discriminator, Generator
 from ..optim import FusedAdam, ema_update
@@ -42,13 +43,35 @@ class CNNTrainer(Trainer):
         g_input = {'mlp': GeneratorInputMLP, 'tiledz': TiledZGeneratorInput}[self.args.g_base]
         act = self.activations[self.args.activation]
         bind = functools.partial
-        return dict(
+        # --spectral-norm: every layer the blocks build through conv_factory (Linear layers and the attention block's own
+        # convolutions stay plain); 'none' binds nothing, so the stock models are built as before
+        sn = self._spectral_norm()
+        g_conv = dict(conv_factory=SpectralNormConv2d) if sn in ('g', 'gd') else {}
+        d_conv = dict(conv_factory=SpectralNormConv2d) if sn in ('d', 'gd') else {}
+        f = dict(
             g_input=bind(g_input, activation_factory=act),
-            g_block=bind(ResidualGeneratorBlock, norm_factory=norm, activation_factory=act),
-            d_block=bind(ResidualDiscriminatorBlock, norm_factory=norm, activation_factory=act),
-            g_output=bind(GeneratorOutput, norm_factory=norm, activation_factory=act),
+            g_block=bind(ResidualGeneratorBlock, norm_factory=norm, activation_factory=act, **g_conv),
+            d_block=bind(ResidualDiscriminatorBlock, norm_factory=norm, activation_factory=act, **d_conv),
+            g_output=bind(GeneratorOutput, norm_factory=norm, activation_factory=act, **g_conv),
             d_output=bind(self.d_output_class, norm_factory=norm, activation_factory=act),
         )
+        if d_conv:
+            f['d_input'] = bind(DiscriminatorInput, **d_conv)
+        return f
+
+    def _spectral_norm(self):
+        return getattr(self.args, 'spectral_norm', 'none')
+
+    def _sn_scope(self, net):
+        """The spectral scope of one network for a span in which its weights are fixed (``functional.spectral_scope``); nothing
+        without --spectral-norm, or with --spectral-per-layer (every forward then iterates and normalises layer by layer)."""
+        if self._spectral_norm() == 'none' or getattr(self.args, 'spectral_per_layer', False):
+            return contextlib.nullcontext()
+        return TF.spectral_scope(net)
+
+    def _sn_backward(self, net):
+        if self._spectral_norm() != 'none' and not getattr(self.args, 'spectral_per_layer', False):
+            TF.spectral_backward(net)
 
     def build_models(self):
         config = self.args.config
@@ -62,13 +85,17 @@ class CNNTrainer(Trainer):
         # construction order g, target_g, d consumes the init RNG like the reference (cnn.py:66-83)
         self.g = make_g()
         self.target_g = make_g()
+        d_input = dict(input_factory=f['d_input']) if 'd_input' in f else {}
         self.d = self.discriminator_class(self.gan_config, block_factory=f['d_block'],
-                                          output_factory=f['d_output']).to(self.device)
+                                          output_factory=f['d_output'], **d_input).to(self.device)
         self.optimizer_g = FusedAdam(self.g, lr=self.args.lr_g, betas=(0., 0.999))
         self.optimizer_d = FusedAdam(self.d, lr=self.args.lr_d, betas=(0., 0.999))
         if self.args.activation == 'selu':
             self.init_params_selu(self.g.parameters())
             self.init_params_selu(self.d.parameters())
+        if self._spectral_norm() != 'none':
+            for net in (self.g, self.target_g, self.d):      # after FusedAdam re-homed the parameters: the item tables hold addresses
+                TF.spectral_store(net)
         self.update_target_generator(1.)     # the reference's "copy weights" (see below)
 
     @torch.no_grad()
@@ -145,7 +172,8 @@ class CNNTrainer(Trainer):
         real = imgs.detach()
         if self.args.grad_penalty:
             real = real.requires_grad_()
-        with TF.filter_forms(self.d):   # the discriminator's parameters are fixed until its optimiser step
+        # (the spectral scope first: the derived filter layouts are taken from the weights it materialises)
+        with self._sn_scope(self.d), TF.filter_forms(self.d):   # the discriminator's parameters are fixed until its optimiser step
             p_real, d_loss = self._d_losses(real, fake, labels)
             d_grad_penalty = None
             if self.args.grad_penalty:
@@ -154,8 +182,19 @@ class CNNTrainer(Trainer):
             # same parameter gradients as d_loss.backward(); naming the leaves just spares autograd the gradient
             # w.r.t. the real images, which the reference computes (real.requires_grad_) and never reads
             with TF.deferred_wgrad(), TF.params_only():     # one launch finishes all conv weight-gradient reductions of this pass
-                torch.autograd.backward(d_loss, inputs=[p for p in self.d.parameters() if p.requires_grad])
+                torch.autograd.backward(d_loss, inputs=self._d_backward_inputs())
+            self._sn_backward(self.d)
         return d_loss.detach(), (d_grad_penalty.detach() if d_grad_penalty is not None else None)
+
+    def _d_backward_inputs(self):
+        """The leaves the D phase's backward is asked for.  Inside a spectral scope the normalised weights are leaves of their
+        own (``functional.spectral_leaves``) and must be named, or autograd prunes their gradients; their ``weight_orig`` get
+        theirs from ``spectral_backward``."""
+        params = [p for p in self.d.parameters() if p.requires_grad]
+        if self._spectral_norm() == 'none' or getattr(self.args, 'spectral_per_layer', False):
+            return params
+        mapped = TF.spectral_original_ids(self.d)
+        return [p for p in params if id(p) not in mapped] + TF.spectral_leaves(self.d)
 
     def _labels(self, bs):
         """(2 bs, 1): ones for the real half, zeros for the fake half (cnn.py:118-121); its first half doubles as the
@@ -240,10 +279,11 @@ class CNNTrainer(Trainer):
 
     def _g_backward(self, fake):
         """Second part (cnn.py:144-148): D(fake) with the stepped discriminator, the loss, g_loss.backward()."""
-        with TF.filter_forms(self.d):
+        with self._sn_scope(self.d), TF.filter_forms(self.d):
             g_loss = self._g_loss(fake, self._labels(len(fake))[:len(fake)])
             with TF.deferred_wgrad():
                 g_loss.backward()
+            self._sn_backward(self.g)
         return g_loss.detach()
 
     def _g_phase(self, bs):
@@ -325,12 +365,13 @@ class CNNTrainer(Trainer):
             self._mode_cache = None          # (a module added since the list was taken is picked up by the next walk)
 
     def _train_batch_eager(self, imgs):
-        d_loss, d_grad_penalty = self._d_phase(imgs)
-        self._begin_reduce('d', self.optimizer_d)          # D-bucket all-reduce under the generator forward below
-        fake = self._g_forward(len(imgs))
-        self._finish_reduce('d')
-        self.optimizer_d.step()
-        g_loss = self._g_backward(fake)
+        with self._sn_scope(self.g):                           # G's weights are fixed until its optimiser step: both forwards read them
+            d_loss, d_grad_penalty = self._d_phase(imgs)
+            self._begin_reduce('d', self.optimizer_d)          # D-bucket all-reduce under the generator forward below
+            fake = self._g_forward(len(imgs))
+            self._finish_reduce('d')
+            self.optimizer_d.step()
+            g_loss = self._g_backward(fake)
         self._begin_reduce('g', self.optimizer_g)
         self._finish_reduce('g')
         self.optimizer_g.step()
@@ -390,23 +431,29 @@ class CNNTrainer(Trainer):
         split = multi and not inside
         if multi:
             kw['capture_error_mode'] = 'thread_local'
-        with torch.cuda.graph(g1, **kw):
-            self._out_d = self._d_phase(self._static_imgs)
-            if inside:
-                dp.all_reduce_mean(self.optimizer_d.grads)
-        if split:           # the generator forward in a graph of its own: it runs while the D bucket is all-reduced
-            with torch.cuda.graph(g2a, **kw):
-                fake = self._g_forward(len(imgs))
-            with torch.cuda.graph(g2b, **kw):
-                self.optimizer_d.apply()
-                self._out_g = self._g_backward(fake)
-        else:
-            g2a = None
-            with torch.cuda.graph(g2b, **kw):
-                self.optimizer_d.apply()
-                self._out_g = self._g_phase(len(imgs))
+        # G's spectral scope spans the graphs up to its backward, as in the eager step; its launches are the first of g1
+        g_scope = contextlib.ExitStack()
+        try:
+            with torch.cuda.graph(g1, **kw):
+                g_scope.enter_context(self._sn_scope(self.g))
+                self._out_d = self._d_phase(self._static_imgs)
                 if inside:
-                    dp.all_reduce_mean(self.optimizer_g.grads)
+                    dp.all_reduce_mean(self.optimizer_d.grads)
+            if split:           # the generator forward in a graph of its own: it runs while the D bucket is all-reduced
+                with torch.cuda.graph(g2a, **kw):
+                    fake = self._g_forward(len(imgs))
+                with torch.cuda.graph(g2b, **kw):
+                    self.optimizer_d.apply()
+                    self._out_g = self._g_backward(fake)
+            else:
+                g2a = None
+                with torch.cuda.graph(g2b, **kw):
+                    self.optimizer_d.apply()
+                    self._out_g = self._g_phase(len(imgs))
+                    if inside:
+                        dp.all_reduce_mean(self.optimizer_g.grads)
+        finally:
+            g_scope.close()
         with torch.cuda.graph(g3, **kw):
             self.optimizer_g.apply()
             self.update_target_generator()
@@ -426,6 +473,9 @@ class CNNTrainer(Trainer):
         # their ids: a model or optimiser swapped from outside -- a resume into a live trainer -- starts at generation 0 again.)
         gen = (self.d, self.optimizer_d, self.optimizer_d.ensure_bound(), self.g, self.optimizer_g, self.optimizer_g.ensure_bound(),
                self.target_g)
+        if self._spectral_norm() != 'none':
+            # the spectral stores' arenas and item tables are baked in too; built (or rebuilt) here, never under capture
+            gen += tuple(getattr(TF.spectral_store(net), 'generation', None) for net in (self.d, self.g, self.target_g))
         if self._graphs is not None and gen != self._graph_gen:
             self._graphs = None                                # parameter buckets were rebuilt, or a model replaced: recapture
         dp = self.data_parallel
@@ -498,6 +548,9 @@ class CNNTrainer(Trainer):
         ``lr`` argument is accepted and ignored: build_models' update_target_generator(1.)
         therefore moves target_g only 1e-3 of the way towards g, it does not copy."""
         ema_update(self.target_g, self.g, self.args.lr_target_g)
+        if self._spectral_norm() in ('g', 'gd'):
+            # the EMA moves parameters only: target_g takes G's u and v as they are (one copy), as BigGAN copies its EMA buffers
+            TF.spectral_sync_uv(self.target_g, self.g)
 
 
 def main():

@@ -203,6 +203,13 @@ class Trainer:
         self.rng_feed = RngFeed(self.device)
         self.rng_feed.mode = 'off'
         self._in_step = False        # True only inside train_batch (and graph capture): draws then go through the feed
+        sn = getattr(args, 'spectral_norm', 'none')
+        if sn not in ('none', 'd', 'g', 'gd'):
+            raise ValueError(f'--spectral-norm {sn!r}: one of none, d, g, gd')
+        if sn != 'none':
+            from .cnn import CNNTrainer
+            if type(self) is not CNNTrainer:
+                raise NotImplementedError(f'--spectral-norm {sn} is implemented for CNNTrainer only, not for {type(self).__name__}')
 
     # ------------------------------------------------------------------ hot-path helpers
     @property
@@ -284,6 +291,10 @@ class Trainer:
         p.add_argument('--g-base', default='mlp')
         p.add_argument('--norm', default='bn')
         p.add_argument('--activation', default='relu')
+        # not in the reference: spectral normalisation of the conv_factory layers of D, G or both
+        p.add_argument('--spectral-norm', choices=('none', 'd', 'g', 'gd'), default='none')
+        p.add_argument('--spectral-per-layer', action='store_true',
+                       help='with --spectral-norm: no spectral scopes, every forward iterates and normalises layer by layer')
 
     @classmethod
     def default_args(cls, **overrides):
