@@ -137,6 +137,21 @@ typedef int64_t tg_host_i64;
 int tg_conv2d_wgrad_partials(const float* x, const float* gy, float* workspace, size_t workspace_bytes,
                              int B, int Cin, int Cout, int H, int W, int ks, int want_bias, void* stream);
 int tg_conv2d_wgrad_reduce_batch(const tg_host_i64* items /*host*/, int n_items, void* stream);
+/* Stage 1 of MANY 1x1 weight gradients in one launch (a backward pass' shortcut, attention-output and theta / phi / g layers: each is a
+ * few microseconds of traffic behind a launch, and nothing reads a weight gradient before the optimiser).  `items` is a HOST array of
+ * n_items x TG_WGRAD1X1_ITEM_FIELDS 64-bit words:
+ *   [0] x (B,Cin,H,W)     [1] gy0 (B,c0,H,W)     [2] gy1 (B,c1,H,W) or 0     [3] gy2 (B,c2,H,W) or 0      (device addresses)
+ *   [4] workspace (device address)                [5] workspace bytes
+ *   [6..8] c0, c1, c2: Cout = c0 + c1 + c2; a plain layer has c1 = c2 = 0 and [2] = [3] = 0, the theta / phi / g form all three
+ *   [9..12] B, Cin, H, W   [13] ks (1: the only family so far)   [14] want_bias
+ * Every row writes what tg_conv2d_wgrad_partials (tg_conv1x1_multi_wgrad's first half for three gy) writes for the same layer, bit for
+ * bit, into a workspace of tg_conv2d_wgrad_workspace(B, Cin, Cout, H, W, 1) bytes: rows of tg_conv2d_wgrad_reduce_batch finish them.
+ * Needs H*W % 16 == 0 (tg_conv1x1_wgrad_batch_supported: the shape part of the rule, host only) and [0]..[4] 16-byte aligned.
+ * Every row is checked before anything is launched: TG_EINVAL / TG_EUNSUPPORTED / TG_EWORKSPACE for the first bad row, nothing
+ * written.  More rows than fit one kernel argument block go into several launches; n_items == 0 is TG_OK with no launch.      */
+#define TG_WGRAD1X1_ITEM_FIELDS 15
+int tg_conv1x1_wgrad_batch_supported(int B, int Cin, int Cout, int H, int W);
+int tg_conv1x1_wgrad_partials_batch(const tg_host_i64* items /*host*/, int n_items, void* stream);
 /* tg_poolconv3x3_weights for n_items layers in one launch (a discriminator's stride-2 layers all need their derived filters at
  * the start of a pass).  `items`: HOST array of n_items x TG_FORM_ITEM_FIELDS words: [0] w  [1] w4  [2] wp (device addresses)
  * [3] Cout  [4] Cin.  Same arithmetic per layer as the single call. */

@@ -1330,13 +1330,15 @@ conv_wgrad_dma_kernel(const float* __restrict__ x, const float* __restrict__ gy,
 // contiguous bytes per wave-load, consecutive groups continue the same rows) and the four components feed four 16x16x4
 // MFMAs (k-step r contracts the pixels {4h + r}).  Per-workgroup partials in the layout of conv_wgrad_kernel (same plan,
 // same reduce kernels, fixed summation order => deterministic); the bias gradient is the sum of the A operands.
+// The body takes its coordinates (split, co tile, ci tile) as arguments: the per-layer kernel passes blockIdx, the grouped
+// kernel below decodes them from a table.  red: 4 MT NT 4 64 + 4 16 MT floats of LDS.
 template <int MT, int NT>
-__global__ void __launch_bounds__(256)
-conv1x1_wgrad_stream_kernel(const float* __restrict__ x, ChanSegs gys, float* __restrict__ part,
-                            float* __restrict__ bias_part /*nullable: [S][Cout]*/, int Cin, int Cout, int HW, int64_t groups, int S) {
-  __shared__ float red[4 * MT * NT * 4 * 64 + 4 * 16 * MT];
+__device__ __forceinline__ void
+conv1x1_wgrad_stream_body(float* red, const float* __restrict__ x, const ChanSegs& gys, float* __restrict__ part,
+                          float* __restrict__ bias_part /*nullable: [S][Cout]*/, int Cin, int Cout, int HW, int64_t groups, int S,
+                          int split, int co_tile, int ci_tile) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, h = lane >> 4;
-  const int co0 = blockIdx.y * 16 * MT, ci0 = blockIdx.z * 16 * NT, split = blockIdx.x;
+  const int co0 = co_tile * 16 * MT, ci0 = ci_tile * 16 * NT;
   const int64_t g_begin = groups * split / S, g_end = groups * (split + 1) / S;
   const int64_t n = g_end - g_begin;
   const int64_t w_begin = g_begin + n * wave / 4, w_end = g_begin + n * (wave + 1) / 4;
@@ -1346,7 +1348,7 @@ conv1x1_wgrad_stream_kernel(const float* __restrict__ x, ChanSegs gys, float* __
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int co = min(co0 + 16 * m + j, Cout - 1), k = gys.find(co);
-    abase[m] = gys.p[k];
+    abase[m] = gys.p[k];                                     // (per-lane index: gys must sit in the argument block, not in a copy)
     aimg[m] = (int64_t)gys.width(k) * HW;
     arow[m] = (int64_t)(co - gys.start[k]) * HW + 4 * h;
   }
@@ -1401,7 +1403,7 @@ conv1x1_wgrad_stream_kernel(const float* __restrict__ x, ChanSegs gys, float* __
 #pragma unroll
       for (int i = 0; i < 4; ++i) red[wave * PER_WAVE + ((m * NT + t) * 4 + i) * 64 + lane] = acc[m][t][i];
   float* bred = red + 4 * PER_WAVE;                          // [wave][16 MT]
-  const bool do_bias = bias_part != nullptr && blockIdx.z == 0;
+  const bool do_bias = bias_part != nullptr && ci_tile == 0;
   if (do_bias) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -1425,13 +1427,65 @@ conv1x1_wgrad_stream_kernel(const float* __restrict__ x, ChanSegs gys, float* __
   }
 }
 
+template <int MT, int NT>
+__global__ void __launch_bounds__(256)
+conv1x1_wgrad_stream_kernel(const float* __restrict__ x, ChanSegs gys, float* __restrict__ part,
+                            float* __restrict__ bias_part /*nullable: [S][Cout]*/, int Cin, int Cout, int HW, int64_t groups, int S) {
+  __shared__ float red[4 * MT * NT * 4 * 64 + 4 * 16 * MT];
+  conv1x1_wgrad_stream_body<MT, NT>(red, x, gys, part, bias_part, Cin, Cout, HW, groups, S, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// The same stage 1 for MANY 1x1 layers in one launch.  In a training step every such layer is 1-4 us of traffic behind
+// ~10 us of ramp, first-load latency and drain, and nothing reads a weight gradient before the optimiser: the layers of a
+// whole backward pass are recorded and run here together.  Items travel in the kernel argument block like ReduceBatch
+// below; a workgroup finds its item by a uniform scan and decodes (split, co tile, ci tile) from its offset inside the
+// item, split fastest as in the per-layer grid.  Same body, same plan => the partials are bit-identical.
+constexpr int W1B_MAX_ITEMS = 40;
+struct Wgrad1x1Item {
+  const float* x;
+  ChanSegs gy;
+  float* part; float* bias_part;                // bias_part null: no bias partials
+  int64_t groups;
+  int Cin, Cout, HW, S;
+};
+struct Wgrad1x1Batch {
+  int n;
+  int block_end[W1B_MAX_ITEMS];                 // exclusive prefix of workgroups per item
+  Wgrad1x1Item item[W1B_MAX_ITEMS];
+};
+static_assert(sizeof(Wgrad1x1Batch) <= 4096, "the table travels in the kernel argument block");
+// 16-channel blocks per workgroup along Cout (MT) and Cin (NT): ONE rule for the per-layer launch and the grouped kernel
+__host__ __device__ static inline int conv1x1_wgrad_mt(int Cout) { return Cout > 16 ? 2 : 1; }
+__host__ __device__ static inline int conv1x1_wgrad_nt(int Cin) { return Cin > 16 ? 2 : 1; }
+
+__global__ void __launch_bounds__(256) conv1x1_wgrad_grouped_kernel(Wgrad1x1Batch tb) {
+  __shared__ float red[4 * 2 * 2 * 4 * 64 + 4 * 16 * 2];              // the <2, 2> variant's; the others use its front
+  int i = 0;
+  while (i + 1 < tb.n && (int)blockIdx.x >= tb.block_end[i]) ++i;      // uniform per workgroup
+  const Wgrad1x1Item& it = tb.item[i];                               // (a reference: the item stays in the argument block)
+  int l = blockIdx.x - (i > 0 ? tb.block_end[i - 1] : 0);
+  const int mt = conv1x1_wgrad_mt(it.Cout), nt = conv1x1_wgrad_nt(it.Cin);
+  const int co_tiles = (it.Cout + 16 * mt - 1) / (16 * mt);
+  const int split = l % it.S;
+  l /= it.S;
+  const int co_tile = l % co_tiles, ci_tile = l / co_tiles;
+  if (mt == 1 && nt == 1)
+    conv1x1_wgrad_stream_body<1, 1>(red, it.x, it.gy, it.part, it.bias_part, it.Cin, it.Cout, it.HW, it.groups, it.S, split, co_tile, ci_tile);
+  else if (mt == 1)
+    conv1x1_wgrad_stream_body<1, 2>(red, it.x, it.gy, it.part, it.bias_part, it.Cin, it.Cout, it.HW, it.groups, it.S, split, co_tile, ci_tile);
+  else if (nt == 1)
+    conv1x1_wgrad_stream_body<2, 1>(red, it.x, it.gy, it.part, it.bias_part, it.Cin, it.Cout, it.HW, it.groups, it.S, split, co_tile, ci_tile);
+  else
+    conv1x1_wgrad_stream_body<2, 2>(red, it.x, it.gy, it.part, it.bias_part, it.Cin, it.Cout, it.HW, it.groups, it.S, split, co_tile, ci_tile);
+}
+
 static inline bool conv1x1_wgrad_stream_ok(const float* x, const float* gy, const Shape& s) {
   return (s.H * s.W) % 16 == 0 && tg_aligned16(x) && tg_aligned16(gy);
 }
 static int launch_conv1x1_wgrad_segs(const float* x, ChanSegs gy, float* part, float* bias_part, Shape s, int S, hipStream_t st) {
   const int HW = s.H * s.W;
   const int64_t groups = (int64_t)s.B * (HW / 16);
-  const int mt = s.Cout > 16 ? 2 : 1, nt = s.Cin > 16 ? 2 : 1;
+  const int mt = conv1x1_wgrad_mt(s.Cout), nt = conv1x1_wgrad_nt(s.Cin);
   dim3 grid(S, (s.Cout + 16 * mt - 1) / (16 * mt), (s.Cin + 16 * nt - 1) / (16 * nt));
   if (mt == 1 && nt == 1) conv1x1_wgrad_stream_kernel<1, 1><<<grid, 256, 0, st>>>(x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S);
   else if (mt == 1) conv1x1_wgrad_stream_kernel<1, 2><<<grid, 256, 0, st>>>(x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S);
@@ -3463,6 +3517,70 @@ int tg_conv2d_wgrad_reduce_batch(const tg_host_i64* items, int n_items, void* st
     wgrad_reduce_batch_kernel<<<blocks, 256, 0, st>>>(rb);
   }
   return tg_launch_status();
+}
+
+// ---- stage 1 of many 1x1 weight gradients in one launch (conv1x1_wgrad_grouped_kernel)
+static inline bool wgrad1x1_shape_ok(int B, int Cin, int Cout, int H, int W) {
+  return check_shape(B, Cin, Cout, H, W, 1) == TG_OK && ((int64_t)H * W) % 16 == 0;
+}
+int tg_conv1x1_wgrad_batch_supported(int B, int Cin, int Cout, int H, int W) { return wgrad1x1_shape_ok(B, Cin, Cout, H, W) ? 1 : 0; }
+
+static int wgrad1x1_check_row(const tg_host_i64* it) {
+  const int64_t c0 = it[6], c1 = it[7], c2 = it[8];
+  for (int f = 6; f <= 14; ++f)
+    if (it[f] < 0 || it[f] > INT32_MAX) return TG_EINVAL;
+  const int B = (int)it[9], Cin = (int)it[10], H = (int)it[11], W = (int)it[12], ks = (int)it[13];
+  if (it[0] == 0 || it[1] == 0 || it[4] == 0 || c0 <= 0 || c0 + c1 + c2 > INT32_MAX) return TG_EINVAL;
+  const bool one = c1 == 0 && c2 == 0 && it[2] == 0 && it[3] == 0, three = c1 > 0 && c2 > 0 && it[2] != 0 && it[3] != 0;
+  if (!one && !three) return TG_EINVAL;
+  const int Cout = (int)(c0 + c1 + c2);
+  if (int rc = check_shape(B, Cin, Cout, H, W, ks)) return rc;
+  if (ks != 1 || !wgrad1x1_shape_ok(B, Cin, Cout, H, W)) return TG_EUNSUPPORTED;
+  for (int f = 0; f <= 4; ++f)
+    if (it[f] & 15) return TG_EUNSUPPORTED;
+  if (it[5] < 0 || (uint64_t)it[5] < tg_conv2d_wgrad_workspace(B, Cin, Cout, H, W, 1)) return TG_EWORKSPACE;
+  return TG_OK;
+}
+
+int tg_conv1x1_wgrad_partials_batch(const tg_host_i64* items, int n_items, void* stream) {
+  if (n_items < 0) return TG_EINVAL;
+  if (n_items == 0) return TG_OK;
+  TG_CHECK_PTR(items);
+  for (int i = 0; i < n_items; ++i)                    // every row before the first launch: a bad row leaves nothing written
+    if (int rc = wgrad1x1_check_row(items + (size_t)i * TG_WGRAD1X1_ITEM_FIELDS)) return rc;
+  hipStream_t st = tg_stream(stream);
+  for (int base = 0; base < n_items;) {
+    Wgrad1x1Batch tb;
+    int64_t blocks = 0;
+    int n = 0;
+    for (; n < W1B_MAX_ITEMS && base + n < n_items; ++n) {
+      const tg_host_i64* it = items + (size_t)(base + n) * TG_WGRAD1X1_ITEM_FIELDS;
+      const int c0 = (int)it[6], c1 = (int)it[7], c2 = (int)it[8], Cout = c0 + c1 + c2;
+      const int B = (int)it[9], Cin = (int)it[10], H = (int)it[11], W = (int)it[12], HW = H * W;
+      const WgPlan p = wgrad_plan(B, Cin, Cout, H, W, 1);
+      const int mt = conv1x1_wgrad_mt(Cout), nt = conv1x1_wgrad_nt(Cin);
+      const int64_t wgs = (int64_t)p.S * ((Cout + 16 * mt - 1) / (16 * mt)) * ((Cin + 16 * nt - 1) / (16 * nt));
+      if (n > 0 && blocks + wgs > INT32_MAX) break;    // (the grid index is 32 bits: the rest goes into the next launch)
+      if (wgs > INT32_MAX) return TG_EUNSUPPORTED;
+      Wgrad1x1Item& w = tb.item[n];
+      float* ws = reinterpret_cast<float*>(it[4]);
+      w.x = reinterpret_cast<const float*>(it[0]);
+      w.gy = c1 ? three_segs(reinterpret_cast<const float*>(it[1]), reinterpret_cast<const float*>(it[2]), reinterpret_cast<const float*>(it[3]), c0, c1, c2)
+                : one_seg(reinterpret_cast<const float*>(it[1]), Cout);
+      w.part = ws;
+      w.bias_part = it[14] ? ws + (size_t)p.S * Cout * Cin : nullptr;
+      w.groups = (int64_t)B * (HW / 16);
+      w.Cin = Cin; w.Cout = Cout; w.HW = HW; w.S = p.S;
+      blocks += wgs;
+      tb.block_end[n] = (int)blocks;
+    }
+    tb.n = n;
+    for (int i = n; i < W1B_MAX_ITEMS; ++i) { tb.block_end[i] = (int)blocks; tb.item[i] = tb.item[0]; }
+    conv1x1_wgrad_grouped_kernel<<<(unsigned)blocks, 256, 0, st>>>(tb);
+    if (int rc = tg_launch_status()) return rc;
+    base += n;
+  }
+  return TG_OK;
 }
 
 }  // extern "C"

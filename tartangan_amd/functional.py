@@ -547,7 +547,43 @@ class _DeferredWgrad:
     active = False
     items = []
     s2_items = []       # the stride-2 forms' rows (tg_s2_wgrad_reduce_batch)
+    stage1 = []         # 1x1 layers whose stage 1 has not run either (tg_conv1x1_wgrad_partials_batch)
     keep = []
+
+
+# 1x1 layers whose x + gy bytes exceed this keep their own stage-1 launch inside ``deferred_wgrad()`` (None: every eligible
+# layer joins the grouped launch).  A large layer already streams near the memory rate on its own, and deferring it means
+# reading a gy again that is no longer cache-warm.  MEASURED: DESIGN.md section 11, "grouped 1x1 weight gradients".
+GROUPED_WGRAD_MAX_BYTES = None
+
+
+def _grouped_stage1_enabled():
+    return not _WgradStream.enabled and hasattr(K(), 'conv1x1_wgrad_partials_batch')
+
+
+def _grouped_stage1(x, gys, ws, cs, want_bias):
+    """Inside ``deferred_wgrad()``: record stage 1 of a 1x1 layer's weight gradient (``gys``: one output gradient, or the three of
+    theta / phi / g) for the ONE grouped launch at the flush and return True -- nothing is launched now.  False: the layer
+    keeps its per-layer launch (no such entry point in the backend, TG_WGRAD_STREAM=1, a shape or an alignment outside the
+    grouped kernel's rule, or over the size cut-off)."""
+    k = K()
+    if not _grouped_stage1_enabled():
+        return False
+    B, Cin, H, W = x.shape
+    ts = (x, *gys, ws)
+    if isinstance(k, _be.HipBackend) and not all(t.is_cuda for t in ts):
+        return False                                    # (the per-layer call then reports the CPU tensor)
+    if not all(t.is_contiguous() and t.dtype == torch.float32 and t.data_ptr() % 16 == 0 for t in ts):
+        return False
+    if not k.conv1x1_wgrad_batch_supported(B, Cin, sum(cs), H, W):
+        return False
+    if GROUPED_WGRAD_MAX_BYTES is not None and 4 * B * H * W * (Cin + sum(cs)) > GROUPED_WGRAD_MAX_BYTES:
+        return False
+    ptrs = [g.data_ptr() for g in gys] + [0] * (3 - len(gys))
+    widths = list(cs) + [0] * (3 - len(cs))
+    _DeferredWgrad.stage1.append([x.data_ptr(), *ptrs, ws.data_ptr(), ws.numel() * 4, *widths, B, Cin, H, W, 1, int(want_bias)])
+    _DeferredWgrad.keep.append(ts)
+    return True
 
 
 @contextlib.contextmanager
@@ -557,7 +593,9 @@ def deferred_wgrad():
     A backward pass runs ~30-50 weight-gradient kernels, each followed by a reduction of its per-workgroup partials
     that is ~1 us of work behind ~5 us of launch latency.  Inside this context the reductions are recorded instead
     and run as ONE launch on exit (``tg_conv2d_wgrad_reduce_batch``; same partials, same summation order, so
-    bit-identical gradients).  Only the trainers use it, around their own ``backward`` calls: until the context
+    bit-identical gradients).  The 1x1 layers (and the theta / phi / g projections) do not even launch their first stage
+    inside the context: they record a row each, and the exit runs all of them as ONE launch in front of the reductions
+    (``tg_conv1x1_wgrad_partials_batch``; again bit-identical).  Only the trainers use it, around their own ``backward`` calls: until the context
     exits the ``.grad`` of conv weights is incomplete, which a foreign training loop could not know.
     """
     outer = _DeferredWgrad.active
@@ -613,7 +651,10 @@ def flush_wgrad():
     if st.items or st.s2_items:
         items, st.items = st.items, []
         s2_items, st.s2_items = st.s2_items, []
+        stage1, st.stage1 = st.stage1, []
         try:
+            if stage1:      # the 1x1 layers that launched nothing so far: their partials, all in one launch, before any reduce
+                K().conv1x1_wgrad_partials_batch(torch.tensor(stage1, dtype=torch.int64), len(stage1))
             # A weight that collected several contributions in this pass (the discriminator sees the real and the
             # fake batch) must not be updated by two workgroups of one launch: contribution k of every weight goes
             # into launch k, in recording order (= the order the per-layer calls would have accumulated in).
@@ -640,8 +681,9 @@ def _conv_wgrad_into(x, gy, gw, gbias, ks, accumulate):
     nbytes = K().conv2d_wgrad_workspace(B, Cin, Cout, H, W, ks)
     if accumulate and _DeferredWgrad.active:
         ws = x.new_empty(nbytes // 4 + 4)               # its own buffer: must survive until the batch reduce
-        with _beside_backward(x, gy, ws):
-            K().conv2d_wgrad_partials(x, gy, ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, int(gbias is not None))
+        if not (ks == 1 and _grouped_stage1(x, (gy,), ws, (Cout,), gbias is not None)):
+            with _beside_backward(x, gy, ws):
+                K().conv2d_wgrad_partials(x, gy, ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, int(gbias is not None))
         _DeferredWgrad.items.append([ws.data_ptr(), gw.data_ptr(), gbias.data_ptr() if gbias is not None else 0,
                                      B, Cin, Cout, H, W, ks, 1])
         _DeferredWgrad.keep.append((ws, gw, gbias))
@@ -1011,6 +1053,14 @@ def _qkv_wgrad(x, gys, ws, need):
         return [_ConvWgrad.apply(x, g, 1) if n else None for g, n in zip(gys, need)]
     B, Cin, H, W = x.shape
     cs = [w.shape[0] for w in ws]
+    if _DeferredWgrad.active and _grouped_stage1_enabled():
+        # an ordinary item of the pass' tables: stage 1 in the grouped launch, one reduce row onto the adjacent .grad matrix
+        C = sum(cs)
+        wsd = x.new_empty(K().conv2d_wgrad_workspace(B, Cin, C, H, W, 1) // 4 + 4)
+        if _grouped_stage1(x, tuple(gys), wsd, cs, False):
+            _DeferredWgrad.items.append([wsd.data_ptr(), cat.data_ptr(), 0, B, Cin, C, H, W, 1, 1])
+            _DeferredWgrad.keep.append((wsd, cat))
+            return [None, None, None]
     nbytes = K().conv1x1_multi_wgrad_workspace(*cs, B, Cin, H, W)
     wsb = _ws(x, nbytes)
     K().conv1x1_multi_wgrad(x, gys[0], gys[1], gys[2], cat, wsb, wsb.numel() * 4, *cs, B, Cin, H, W, 1)
