@@ -131,7 +131,13 @@ int tg_conv1x1_multi_wgrad(const float* x, const float* gy0, const float* gy1, c
  *                                  [3..8] B, Cin, Cout, H, W, ks     [9] accumulate
  * Results are bit-identical to tg_conv2d_wgrad (same partials, same summation order).  Within one call every
  * gw / gbias may appear at most once (items are reduced concurrently); further contributions to the same
- * gradient go into a later call.                                                                           */
+ * gradient go into a later call.
+ *
+ * THE TABLE CONTRACT of the four entry points that take such a host table (tg_conv2d_wgrad_reduce_batch,
+ * tg_conv1x1_wgrad_partials_batch, tg_poolconv3x3_weights_batch, tg_s2_wgrad_reduce_batch): `items` is read during the call only.
+ * Every row is checked before anything is launched: the first bad row's code (TG_EINVAL / TG_EUNSUPPORTED / TG_EWORKSPACE) is
+ * returned with nothing written.  More rows than one kernel argument block holds go into several launches; n_items == 0 is
+ * TG_OK with no launch, n_items < 0 or a null `items` TG_EINVAL.                                                            */
 typedef int64_t tg_host_i64;
 #define TG_WGRAD_ITEM_FIELDS 10
 int tg_conv2d_wgrad_partials(const float* x, const float* gy, float* workspace, size_t workspace_bytes,
@@ -147,21 +153,20 @@ int tg_conv2d_wgrad_reduce_batch(const tg_host_i64* items /*host*/, int n_items,
  * Every row writes what tg_conv2d_wgrad_partials (tg_conv1x1_multi_wgrad's first half for three gy) writes for the same layer, bit for
  * bit, into a workspace of tg_conv2d_wgrad_workspace(B, Cin, Cout, H, W, 1) bytes: rows of tg_conv2d_wgrad_reduce_batch finish them.
  * Needs H*W % 16 == 0 (tg_conv1x1_wgrad_batch_supported: the shape part of the rule, host only) and [0]..[4] 16-byte aligned.
- * Every row is checked before anything is launched: TG_EINVAL / TG_EUNSUPPORTED / TG_EWORKSPACE for the first bad row, nothing
- * written.  More rows than fit one kernel argument block go into several launches; n_items == 0 is TG_OK with no launch.      */
+ * The table contract above holds.                                                                                              */
 #define TG_WGRAD1X1_ITEM_FIELDS 15
 int tg_conv1x1_wgrad_batch_supported(int B, int Cin, int Cout, int H, int W);
 int tg_conv1x1_wgrad_partials_batch(const tg_host_i64* items /*host*/, int n_items, void* stream);
 /* tg_poolconv3x3_weights for n_items layers in one launch (a discriminator's stride-2 layers all need their derived filters at
  * the start of a pass).  `items`: HOST array of n_items x TG_FORM_ITEM_FIELDS words: [0] w  [1] w4  [2] wp (device addresses)
- * [3] Cout  [4] Cin.  Same arithmetic per layer as the single call. */
+ * [3] Cout  [4] Cin.  Same arithmetic per layer as the single call; the table contract above holds. */
 #define TG_FORM_ITEM_FIELDS 5
 int tg_poolconv3x3_weights_batch(const tg_host_i64* items /*host*/, int n_items, void* stream);
 /* The stride-2 weight gradients in two steps, like tg_conv2d_wgrad_partials / _reduce_batch: stage 1 per layer into a workspace of its
  * own (tg_*_wgrad_workspace bytes, untouched until the reduce has run), then ONE launch that sums, folds onto the 3x3 taps and
  * finishes the bias gradients of all recorded layers.  Items as for tg_conv2d_wgrad_reduce_batch with [8] = 0 (pooled conv: stage 1
  * by tg_poolconv3x3_wgrad_partials) or 1 (up-conv: tg_upconv3x3_wgrad_partials) in the place of ks; (B, ., H, W) the LOW-resolution
- * plane; [2] gbias nonzero needs want_bias != 0 in stage 1.  Bit-identical to the one-call forms.                               */
+ * plane; [2] gbias nonzero needs want_bias != 0 in stage 1.  Bit-identical to the one-call forms; the table contract above holds. */
 /* The discriminator's from-RGB 1x1 convolution composed into the 3x3 convolution that follows it (discriminator.py:11-22 + :60-61,
  * nothing in between): wc [Cout][Cimg + 1][3][3] = sum_m [w1 | b1][m][c] * w3[co][m][tap] (the from-RGB bias on an all-ones input channel),
  * and its backward (gw1 [C][Cimg], gb1 [C], gw3 [Cout][C][3][3]; accumulate: += into all three).  One launch each.          */

@@ -24,6 +24,7 @@
 #include <utility>
 
 #include "common.h"
+#include "grouped.h"
 
 namespace {
 
@@ -1437,10 +1438,9 @@ conv1x1_wgrad_stream_kernel(const float* __restrict__ x, ChanSegs gys, float* __
 
 // The same stage 1 for MANY 1x1 layers in one launch.  In a training step every such layer is 1-4 us of traffic behind
 // ~10 us of ramp, first-load latency and drain, and nothing reads a weight gradient before the optimiser: the layers of a
-// whole backward pass are recorded and run here together.  Items travel in the kernel argument block like ReduceBatch
-// below; a workgroup finds its item by a uniform scan and decodes (split, co tile, ci tile) from its offset inside the
-// item, split fastest as in the per-layer grid.  Same body, same plan => the partials are bit-identical.
-constexpr int W1B_MAX_ITEMS = 40;
+// whole backward pass are recorded and run here together.  Items travel in a grouped-launch table (grouped.h); a
+// workgroup decodes (split, co tile, ci tile) from its offset inside the item, split fastest as in the per-layer grid.
+// Same body, same plan => the partials are bit-identical.
 struct Wgrad1x1Item {
   const float* x;
   ChanSegs gy;
@@ -1448,22 +1448,15 @@ struct Wgrad1x1Item {
   int64_t groups;
   int Cin, Cout, HW, S;
 };
-struct Wgrad1x1Batch {
-  int n;
-  int block_end[W1B_MAX_ITEMS];                 // exclusive prefix of workgroups per item
-  Wgrad1x1Item item[W1B_MAX_ITEMS];
-};
-static_assert(sizeof(Wgrad1x1Batch) <= 4096, "the table travels in the kernel argument block");
+using Wgrad1x1Batch = TgGroupTable<Wgrad1x1Item, 40>;
 // 16-channel blocks per workgroup along Cout (MT) and Cin (NT): ONE rule for the per-layer launch and the grouped kernel
 __host__ __device__ static inline int conv1x1_wgrad_mt(int Cout) { return Cout > 16 ? 2 : 1; }
 __host__ __device__ static inline int conv1x1_wgrad_nt(int Cin) { return Cin > 16 ? 2 : 1; }
 
 __global__ void __launch_bounds__(256) conv1x1_wgrad_grouped_kernel(Wgrad1x1Batch tb) {
   __shared__ float red[4 * 2 * 2 * 4 * 64 + 4 * 16 * 2];              // the <2, 2> variant's; the others use its front
-  int i = 0;
-  while (i + 1 < tb.n && (int)blockIdx.x >= tb.block_end[i]) ++i;      // uniform per workgroup
-  const Wgrad1x1Item& it = tb.item[i];                               // (a reference: the item stays in the argument block)
-  int l = blockIdx.x - (i > 0 ? tb.block_end[i - 1] : 0);
+  int l;
+  const Wgrad1x1Item& it = tg_group_item(tb, &l);
   const int mt = conv1x1_wgrad_mt(it.Cout), nt = conv1x1_wgrad_nt(it.Cin);
   const int co_tiles = (it.Cout + 16 * mt - 1) / (16 * mt);
   const int split = l % it.S;
@@ -1539,25 +1532,16 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 }
 
 // The same reduction for MANY layers in one launch (a whole backward pass' worth of partials): the per-layer
-// reduce is ~5 us of launch latency for ~1 us of work, ~100 times per training step.  Items travel in the kernel
-// argument block (no table in memory to keep alive or copy), a workgroup finds its item by scanning <= MAX_ITEMS
-// block offsets.
-constexpr int RB_MAX_ITEMS = 40;
+// reduce is ~5 us of launch latency for ~1 us of work, ~100 times per training step (grouped.h).
 struct ReduceItem {
   const float* part; float* gw; float* gbias;   // gbias null: no bias gradient; bias partials sit at part + S*E
   int64_t E;
   int S, Cout, accumulate, pad;
 };
-struct ReduceBatch {
-  int n;
-  int block_end[RB_MAX_ITEMS];                  // exclusive prefix of workgroups per item
-  ReduceItem item[RB_MAX_ITEMS];
-};
+using ReduceBatch = TgGroupTable<ReduceItem, 40>;
 __global__ void __launch_bounds__(256) wgrad_reduce_batch_kernel(ReduceBatch rb) {
-  int i = 0;
-  while (i + 1 < rb.n && (int)blockIdx.x >= rb.block_end[i]) ++i;     // uniform per workgroup
-  const ReduceItem it = rb.item[i];
-  const int blk = blockIdx.x - (i > 0 ? rb.block_end[i - 1] : 0);
+  int blk;
+  const ReduceItem& it = tg_group_item(rb, &blk);
   wgrad_reduce_block(blk, it.part, it.gw, it.E, it.S, it.gbias ? it.part + (int64_t)it.S * it.E : nullptr, it.gbias, it.Cout,
                      it.accumulate);
 }
@@ -2591,16 +2575,13 @@ __global__ void __launch_bounds__(256) s2wgrad_reduce_fold_kernel(const float* _
   s2wgrad_reduce_fold(part, gw, S, Clo, Chi, Cout, Cin, mode, accumulate, bias_part, gbias, pair_blocks, (int)blockIdx.x);
 }
 // ... for the stride-2 layers of a whole backward pass in one launch (tg_s2_wgrad_reduce_batch)
-constexpr int SB_MAX_ITEMS = 16;
 struct FoldItem { const float* part; float* gw; const float* bias_part; float* gbias; int S, Clo, Chi, Cout, Cin, mode, accumulate, pair_blocks; };
-struct FoldBatch { FoldItem item[SB_MAX_ITEMS]; int block_end[SB_MAX_ITEMS]; int n; };
+using FoldBatch = TgGroupTable<FoldItem, 16>;
 __global__ void __launch_bounds__(256) s2wgrad_reduce_fold_batch_kernel(FoldBatch fb) {
-  int i = 0;
-  while (i + 1 < fb.n && (int)blockIdx.x >= fb.block_end[i]) ++i;            // (block-uniform)
-  const int first = i == 0 ? 0 : fb.block_end[i - 1];
-  const FoldItem& it = fb.item[i];
+  int blk;
+  const FoldItem& it = tg_group_item(fb, &blk);
   s2wgrad_reduce_fold(it.part, it.gw, it.S, it.Clo, it.Chi, it.Cout, it.Cin, it.mode, it.accumulate, it.bias_part, it.gbias,
-                      it.pair_blocks, (int)blockIdx.x - first);
+                      it.pair_blocks, blk);
 }
 
 // AvgPool2d(2) o conv3x3 = 0.25 * (transpose of the up-conv with the flipped, transposed filter): the same two kernels
@@ -2645,15 +2626,12 @@ __global__ void __launch_bounds__(256) poolconv_weights_kernel(const float* __re
   poolconv_weights_one(w, w4, wp, Cout, Cin, blockIdx.x * 256 + threadIdx.x);
 }
 // ... of several layers in one launch (a network's stride-2 layers all need theirs at the start of a pass)
-constexpr int FB_MAX_ITEMS = 16;
 struct FormItem { const float* w; float* w4; float* wp; int Cout, Cin; };
-struct FormBatch { FormItem item[FB_MAX_ITEMS]; int block_end[FB_MAX_ITEMS]; int n; };
+using FormBatch = TgGroupTable<FormItem, 16>;
 __global__ void __launch_bounds__(256) poolconv_weights_batch_kernel(FormBatch fb) {
-  int i = 0;
-  while (i + 1 < fb.n && (int)blockIdx.x >= fb.block_end[i]) ++i;            // (block-uniform)
-  const int first = i == 0 ? 0 : fb.block_end[i - 1];
-  const FormItem& it = fb.item[i];
-  poolconv_weights_one(it.w, it.w4, it.wp, it.Cout, it.Cin, ((int)blockIdx.x - first) * 256 + threadIdx.x);
+  int blk;
+  const FormItem& it = tg_group_item(fb, &blk);
+  poolconv_weights_one(it.w, it.w4, it.wp, it.Cout, it.Cin, blk * 256 + threadIdx.x);
 }
 
 // =========================================================================== from-RGB 1x1 composed into the first 3x3
@@ -3262,29 +3240,23 @@ int tg_upconv3x3_wgrad_partials(const float* a, const float* gy, float* workspac
   return s2_wgrad_stage1(gy, a, workspace, workspace_bytes, B, Cin, Cout, H, W, 1, want_bias, tg_stream(stream));
 }
 int tg_s2_wgrad_reduce_batch(const tg_host_i64* items, int n_items, void* stream) {
-  if (n_items < 0) return TG_EINVAL;
-  if (n_items == 0) return TG_OK;
-  TG_CHECK_PTR(items);
   hipStream_t st = tg_stream(stream);
-  for (int base = 0; base < n_items; base += SB_MAX_ITEMS) {
-    FoldBatch fb;
-    fb.n = n_items - base < SB_MAX_ITEMS ? n_items - base : SB_MAX_ITEMS;
-    int blocks = 0;
-    for (int i = 0; i < fb.n; ++i) {
-      const tg_host_i64* it = items + (size_t)(base + i) * TG_WGRAD_ITEM_FIELDS;
-      const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], mode = (int)it[8];
-      if (it[0] == 0 || it[1] == 0 || (mode != 0 && mode != 1)) return TG_EINVAL;
-      const int Clo = mode == 0 ? Cout : Cin, Chi = mode == 0 ? Cin : Cout;
-      if (!s2_geo(pick_geo(H, W)) || check_shape(B, Clo, Chi, 2 * H, 2 * W, 3) != TG_OK) return TG_EUNSUPPORTED;
-      fb.item[i] = s2_fold_item(reinterpret_cast<const float*>(it[0]), reinterpret_cast<float*>(it[1]), reinterpret_cast<float*>(it[2]),
-                                B, Clo, Chi, H, W, Cout, Cin, mode, (int)it[9]);
-      blocks += fb.item[i].pair_blocks + (fb.item[i].gbias ? (Cout + 3) / 4 : 0);
-      fb.block_end[i] = blocks;
-    }
-    for (int i = fb.n; i < SB_MAX_ITEMS; ++i) { fb.item[i] = fb.item[0]; fb.block_end[i] = blocks; }
-    s2wgrad_reduce_fold_batch_kernel<<<blocks, 256, 0, st>>>(fb);
-  }
-  return tg_launch_status();
+  return tg_group_run<FoldBatch>(
+      items, n_items, TG_WGRAD_ITEM_FIELDS,
+      [](const tg_host_i64* it) {
+        const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], mode = (int)it[8];
+        if (it[0] == 0 || it[1] == 0 || (mode != 0 && mode != 1)) return (int)TG_EINVAL;
+        const int Clo = mode == 0 ? Cout : Cin, Chi = mode == 0 ? Cin : Cout;
+        if (!s2_geo(pick_geo(H, W)) || check_shape(B, Clo, Chi, 2 * H, 2 * W, 3) != TG_OK) return (int)TG_EUNSUPPORTED;
+        return (int)TG_OK;
+      },
+      [](const tg_host_i64* it, FoldItem* f) {
+        const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], mode = (int)it[8];
+        *f = s2_fold_item(reinterpret_cast<const float*>(it[0]), reinterpret_cast<float*>(it[1]), reinterpret_cast<float*>(it[2]), B,
+                          mode == 0 ? Cout : Cin, mode == 0 ? Cin : Cout, H, W, Cout, Cin, mode, (int)it[9]);
+        return (int64_t)f->pair_blocks + (f->gbias ? (Cout + 3) / 4 : 0);
+      },
+      [st](const FoldBatch& fb, unsigned blocks) { s2wgrad_reduce_fold_batch_kernel<<<blocks, 256, 0, st>>>(fb); });
 }
 
 size_t tg_poolconv3x3_wgrad_workspace(int B, int Cin, int Cout, int H, int W) {
@@ -3322,26 +3294,18 @@ int tg_rgb_compose_bwd(const float* gwc, const float* w1, const float* b1, const
 }
 
 int tg_poolconv3x3_weights_batch(const tg_host_i64* items, int n_items, void* stream) {
-  if (n_items < 0) return TG_EINVAL;
-  if (n_items == 0) return TG_OK;
-  TG_CHECK_PTR(items);
   hipStream_t st = tg_stream(stream);
-  for (int base = 0; base < n_items; base += FB_MAX_ITEMS) {
-    FormBatch fb;
-    fb.n = n_items - base < FB_MAX_ITEMS ? n_items - base : FB_MAX_ITEMS;
-    int blocks = 0;
-    for (int i = 0; i < fb.n; ++i) {
-      const tg_host_i64* it = items + (size_t)(base + i) * TG_FORM_ITEM_FIELDS;
-      const int Cout = (int)it[3], Cin = (int)it[4];
-      if (it[0] == 0 || it[1] == 0 || it[2] == 0 || Cout <= 0 || Cin <= 0) return TG_EINVAL;
-      fb.item[i] = FormItem{reinterpret_cast<const float*>(it[0]), reinterpret_cast<float*>(it[1]), reinterpret_cast<float*>(it[2]), Cout, Cin};
-      blocks += (Cout * Cin + 255) / 256;
-      fb.block_end[i] = blocks;
-    }
-    for (int i = fb.n; i < FB_MAX_ITEMS; ++i) { fb.item[i] = fb.item[0]; fb.block_end[i] = blocks; }
-    poolconv_weights_batch_kernel<<<blocks, 256, 0, st>>>(fb);
-  }
-  return tg_launch_status();
+  return tg_group_run<FormBatch>(
+      items, n_items, TG_FORM_ITEM_FIELDS,
+      [](const tg_host_i64* it) {
+        return it[0] == 0 || it[1] == 0 || it[2] == 0 || (int)it[3] <= 0 || (int)it[4] <= 0 ? (int)TG_EINVAL : (int)TG_OK;
+      },
+      [](const tg_host_i64* it, FormItem* f) {
+        const int Cout = (int)it[3], Cin = (int)it[4];
+        *f = FormItem{reinterpret_cast<const float*>(it[0]), reinterpret_cast<float*>(it[1]), reinterpret_cast<float*>(it[2]), Cout, Cin};
+        return (int64_t)((Cout * Cin + 255) / 256);
+      },
+      [st](const FormBatch& fb, unsigned blocks) { poolconv_weights_batch_kernel<<<blocks, 256, 0, st>>>(fb); });
 }
 
 int tg_poolconv3x3_weights(const float* w, float* w4, float* wp, int Cout, int Cin, void* stream) {
@@ -3488,35 +3452,26 @@ int tg_conv1x1_multi_wgrad(const float* x, const float* gy0, const float* gy1, c
 }
 
 int tg_conv2d_wgrad_reduce_batch(const tg_host_i64* items, int n_items, void* stream) {
-  if (n_items < 0) return TG_EINVAL;
-  if (n_items == 0) return TG_OK;
-  TG_CHECK_PTR(items);
   hipStream_t st = tg_stream(stream);
-  for (int base = 0; base < n_items; base += RB_MAX_ITEMS) {
-    ReduceBatch rb;
-    rb.n = n_items - base < RB_MAX_ITEMS ? n_items - base : RB_MAX_ITEMS;
-    int blocks = 0;
-    for (int i = 0; i < rb.n; ++i) {
-      const tg_host_i64* it = items + (size_t)(base + i) * TG_WGRAD_ITEM_FIELDS;
-      const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], ks = (int)it[8];
-      if (it[0] == 0 || it[1] == 0) return TG_EINVAL;
-      if (int rc = check_shape(B, Cin, Cout, H, W, ks)) return rc;
-      ReduceItem& r = rb.item[i];
-      r.part = reinterpret_cast<const float*>(it[0]);
-      r.gw = reinterpret_cast<float*>(it[1]);
-      r.gbias = reinterpret_cast<float*>(it[2]);
-      r.E = (int64_t)Cout * Cin * ks * ks;
-      r.S = wgrad_plan(B, Cin, Cout, H, W, ks).S;
-      r.Cout = Cout;
-      r.accumulate = (int)it[9];
-      r.pad = 0;
-      blocks += (int)((r.E + 63) / 64) + (r.gbias ? (Cout + 63) / 64 : 0);
-      rb.block_end[i] = blocks;
-    }
-    for (int i = rb.n; i < RB_MAX_ITEMS; ++i) rb.block_end[i] = blocks;
-    wgrad_reduce_batch_kernel<<<blocks, 256, 0, st>>>(rb);
-  }
-  return tg_launch_status();
+  return tg_group_run<ReduceBatch>(
+      items, n_items, TG_WGRAD_ITEM_FIELDS,
+      [](const tg_host_i64* it) {
+        if (it[0] == 0 || it[1] == 0) return (int)TG_EINVAL;
+        return (int)check_shape((int)it[3], (int)it[4], (int)it[5], (int)it[6], (int)it[7], (int)it[8]);
+      },
+      [](const tg_host_i64* it, ReduceItem* r) {
+        const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], ks = (int)it[8];
+        r->part = reinterpret_cast<const float*>(it[0]);
+        r->gw = reinterpret_cast<float*>(it[1]);
+        r->gbias = reinterpret_cast<float*>(it[2]);
+        r->E = (int64_t)Cout * Cin * ks * ks;
+        r->S = wgrad_plan(B, Cin, Cout, H, W, ks).S;
+        r->Cout = Cout;
+        r->accumulate = (int)it[9];
+        r->pad = 0;
+        return (r->E + 63) / 64 + (r->gbias ? (Cout + 63) / 64 : 0);
+      },
+      [st](const ReduceBatch& rb, unsigned blocks) { wgrad_reduce_batch_kernel<<<blocks, 256, 0, st>>>(rb); });
 }
 
 // ---- stage 1 of many 1x1 weight gradients in one launch (conv1x1_wgrad_grouped_kernel)
@@ -3543,44 +3498,25 @@ static int wgrad1x1_check_row(const tg_host_i64* it) {
 }
 
 int tg_conv1x1_wgrad_partials_batch(const tg_host_i64* items, int n_items, void* stream) {
-  if (n_items < 0) return TG_EINVAL;
-  if (n_items == 0) return TG_OK;
-  TG_CHECK_PTR(items);
-  for (int i = 0; i < n_items; ++i)                    // every row before the first launch: a bad row leaves nothing written
-    if (int rc = wgrad1x1_check_row(items + (size_t)i * TG_WGRAD1X1_ITEM_FIELDS)) return rc;
   hipStream_t st = tg_stream(stream);
-  for (int base = 0; base < n_items;) {
-    Wgrad1x1Batch tb;
-    int64_t blocks = 0;
-    int n = 0;
-    for (; n < W1B_MAX_ITEMS && base + n < n_items; ++n) {
-      const tg_host_i64* it = items + (size_t)(base + n) * TG_WGRAD1X1_ITEM_FIELDS;
-      const int c0 = (int)it[6], c1 = (int)it[7], c2 = (int)it[8], Cout = c0 + c1 + c2;
-      const int B = (int)it[9], Cin = (int)it[10], H = (int)it[11], W = (int)it[12], HW = H * W;
-      const WgPlan p = wgrad_plan(B, Cin, Cout, H, W, 1);
-      const int mt = conv1x1_wgrad_mt(Cout), nt = conv1x1_wgrad_nt(Cin);
-      const int64_t wgs = (int64_t)p.S * ((Cout + 16 * mt - 1) / (16 * mt)) * ((Cin + 16 * nt - 1) / (16 * nt));
-      if (n > 0 && blocks + wgs > INT32_MAX) break;    // (the grid index is 32 bits: the rest goes into the next launch)
-      if (wgs > INT32_MAX) return TG_EUNSUPPORTED;
-      Wgrad1x1Item& w = tb.item[n];
-      float* ws = reinterpret_cast<float*>(it[4]);
-      w.x = reinterpret_cast<const float*>(it[0]);
-      w.gy = c1 ? three_segs(reinterpret_cast<const float*>(it[1]), reinterpret_cast<const float*>(it[2]), reinterpret_cast<const float*>(it[3]), c0, c1, c2)
-                : one_seg(reinterpret_cast<const float*>(it[1]), Cout);
-      w.part = ws;
-      w.bias_part = it[14] ? ws + (size_t)p.S * Cout * Cin : nullptr;
-      w.groups = (int64_t)B * (HW / 16);
-      w.Cin = Cin; w.Cout = Cout; w.HW = HW; w.S = p.S;
-      blocks += wgs;
-      tb.block_end[n] = (int)blocks;
-    }
-    tb.n = n;
-    for (int i = n; i < W1B_MAX_ITEMS; ++i) { tb.block_end[i] = (int)blocks; tb.item[i] = tb.item[0]; }
-    conv1x1_wgrad_grouped_kernel<<<(unsigned)blocks, 256, 0, st>>>(tb);
-    if (int rc = tg_launch_status()) return rc;
-    base += n;
-  }
-  return TG_OK;
+  return tg_group_run<Wgrad1x1Batch>(
+      items, n_items, TG_WGRAD1X1_ITEM_FIELDS, wgrad1x1_check_row,
+      [](const tg_host_i64* it, Wgrad1x1Item* w) {
+        const int c0 = (int)it[6], c1 = (int)it[7], c2 = (int)it[8], Cout = c0 + c1 + c2;
+        const int B = (int)it[9], Cin = (int)it[10], H = (int)it[11], W = (int)it[12], HW = H * W;
+        const WgPlan p = wgrad_plan(B, Cin, Cout, H, W, 1);
+        const int mt = conv1x1_wgrad_mt(Cout), nt = conv1x1_wgrad_nt(Cin);
+        float* ws = reinterpret_cast<float*>(it[4]);
+        w->x = reinterpret_cast<const float*>(it[0]);
+        w->gy = c1 ? three_segs(reinterpret_cast<const float*>(it[1]), reinterpret_cast<const float*>(it[2]), reinterpret_cast<const float*>(it[3]), c0, c1, c2)
+                   : one_seg(reinterpret_cast<const float*>(it[1]), Cout);
+        w->part = ws;
+        w->bias_part = it[14] ? ws + (size_t)p.S * Cout * Cin : nullptr;
+        w->groups = (int64_t)B * (HW / 16);
+        w->Cin = Cin; w->Cout = Cout; w->HW = HW; w->S = p.S;
+        return (int64_t)p.S * ((Cout + 16 * mt - 1) / (16 * mt)) * ((Cin + 16 * nt - 1) / (16 * nt));
+      },
+      [st](const Wgrad1x1Batch& tb, unsigned blocks) { conv1x1_wgrad_grouped_kernel<<<blocks, 256, 0, st>>>(tb); });
 }
 
 }  // extern "C"

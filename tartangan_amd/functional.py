@@ -551,21 +551,20 @@ class _DeferredWgrad:
     keep = []
 
 
-# 1x1 layers whose x + gy bytes exceed this keep their own stage-1 launch inside ``deferred_wgrad()`` (None: every eligible
-# layer joins the grouped launch).  A large layer already streams near the memory rate on its own, and deferring it means
-# reading a gy again that is no longer cache-warm.  MEASURED: DESIGN.md section 11, "grouped 1x1 weight gradients".
-GROUPED_WGRAD_MAX_BYTES = None
+def _host_rows(rows):
+    """(host table, row count): the two leading arguments of every ``*_batch`` entry point."""
+    return torch.tensor(rows, dtype=torch.int64), len(rows)
 
 
 def _grouped_stage1_enabled():
-    return not _WgradStream.enabled and hasattr(K(), 'conv1x1_wgrad_partials_batch')
+    return hasattr(K(), 'conv1x1_wgrad_partials_batch')
 
 
 def _grouped_stage1(x, gys, ws, cs, want_bias):
     """Inside ``deferred_wgrad()``: record stage 1 of a 1x1 layer's weight gradient (``gys``: one output gradient, or the three of
     theta / phi / g) for the ONE grouped launch at the flush and return True -- nothing is launched now.  False: the layer
-    keeps its per-layer launch (no such entry point in the backend, TG_WGRAD_STREAM=1, a shape or an alignment outside the
-    grouped kernel's rule, or over the size cut-off)."""
+    keeps its per-layer launch (no such entry point in the backend, or a shape or an alignment outside the grouped kernel's
+    rule)."""
     k = K()
     if not _grouped_stage1_enabled():
         return False
@@ -576,8 +575,6 @@ def _grouped_stage1(x, gys, ws, cs, want_bias):
     if not all(t.is_contiguous() and t.dtype == torch.float32 and t.data_ptr() % 16 == 0 for t in ts):
         return False
     if not k.conv1x1_wgrad_batch_supported(B, Cin, sum(cs), H, W):
-        return False
-    if GROUPED_WGRAD_MAX_BYTES is not None and 4 * B * H * W * (Cin + sum(cs)) > GROUPED_WGRAD_MAX_BYTES:
         return False
     ptrs = [g.data_ptr() for g in gys] + [0] * (3 - len(gys))
     widths = list(cs) + [0] * (3 - len(cs))
@@ -609,70 +606,32 @@ def deferred_wgrad():
             flush_wgrad()
 
 
-class _WgradStream:
-    """Weight gradients beside the backward's critical path.  In a backward pass the chain is
-    BatchNorm backward (HBM-bound) -> input-gradient convolution (MFMA) -> BatchNorm backward -> ...; a layer's weight
-    gradient hangs off the side of it (it needs the same gy, nothing downstream needs its result before the optimiser).
-    Inside ``deferred_wgrad()`` those launches go to a second stream that forks from the current one where gy is ready and
-    joins it again when the context exits: the MFMA-bound weight gradients then run under the bandwidth-bound BatchNorm
-    passes of the layers below.  Only gradients that accumulate straight into ``.grad`` take this path (nothing on the main
-    stream reads them before the join); their operands are kept alive until the join.
-    MEASURED (round 3, 128:3 batch 64, graph replay, same box back to back): 10.49 / 10.52 ms per step with it, 9.90 / 9.86
-    without -- the co-running kernels take LDS and issue slots from the convolution kernels on the critical path, which lose
-    more than the overlap gains (round 1 found the same with its register-staged kernels).  OFF unless TG_WGRAD_STREAM=1."""
-    import os as _os
-    enabled = _os.environ.get('TG_WGRAD_STREAM', '0') == '1'
-    stream = None
-    used = False
-
-
-@contextlib.contextmanager
-def _beside_backward(*operands):
-    st = _WgradStream
-    if not (st.enabled and _DeferredWgrad.active and operands[0].is_cuda):
-        yield
-        return
-    if st.stream is None:
-        st.stream = torch.cuda.Stream()
-    st.stream.wait_stream(torch.cuda.current_stream())
-    _DeferredWgrad.keep.append(operands)
-    st.used = True
-    with torch.cuda.stream(st.stream):
-        yield
-
-
 def flush_wgrad():
     st = _DeferredWgrad
-    if _WgradStream.used:
-        torch.cuda.current_stream().wait_stream(_WgradStream.stream)
-        _WgradStream.used = False
-        if not st.items and not st.s2_items:
-            st.keep = []
-    if st.items or st.s2_items:
-        items, st.items = st.items, []
-        s2_items, st.s2_items = st.s2_items, []
-        stage1, st.stage1 = st.stage1, []
-        try:
-            if stage1:      # the 1x1 layers that launched nothing so far: their partials, all in one launch, before any reduce
-                K().conv1x1_wgrad_partials_batch(torch.tensor(stage1, dtype=torch.int64), len(stage1))
-            # A weight that collected several contributions in this pass (the discriminator sees the real and the
-            # fake batch) must not be updated by two workgroups of one launch: contribution k of every weight goes
-            # into launch k, in recording order (= the order the per-layer calls would have accumulated in).
-            def in_rounds(table):
-                rounds, seen = [], {}
-                for row in table:
-                    k = seen.get(row[1], 0)
-                    seen[row[1]] = k + 1
-                    if k == len(rounds):
-                        rounds.append([])
-                    rounds[k].append(row)
-                return rounds
-            for rows in in_rounds(items):
-                K().conv2d_wgrad_reduce_batch(torch.tensor(rows, dtype=torch.int64), len(rows))
-            for rows in in_rounds(s2_items):          # (a layer is one form or the other: the two tables share no gradient)
-                K().s2_wgrad_reduce_batch(torch.tensor(rows, dtype=torch.int64), len(rows))
-        finally:
-            st.keep = []
+    items, st.items = st.items, []
+    s2_items, st.s2_items = st.s2_items, []
+    stage1, st.stage1 = st.stage1, []
+    try:
+        if stage1:      # the 1x1 layers that launched nothing so far: their partials, all in one launch, before any reduce
+            K().conv1x1_wgrad_partials_batch(*_host_rows(stage1))
+        # A weight that collected several contributions in this pass (the discriminator sees the real and the
+        # fake batch) must not be updated by two workgroups of one launch: contribution k of every weight goes
+        # into launch k, in recording order (= the order the per-layer calls would have accumulated in).
+        def in_rounds(table):
+            rounds, seen = [], {}
+            for row in table:
+                k = seen.get(row[1], 0)
+                seen[row[1]] = k + 1
+                if k == len(rounds):
+                    rounds.append([])
+                rounds[k].append(row)
+            return rounds
+        for rows in in_rounds(items):
+            K().conv2d_wgrad_reduce_batch(*_host_rows(rows))
+        for rows in in_rounds(s2_items):          # (a layer is one form or the other: the two tables share no gradient)
+            K().s2_wgrad_reduce_batch(*_host_rows(rows))
+    finally:
+        st.keep = []
 
 
 def _conv_wgrad_into(x, gy, gw, gbias, ks, accumulate):
@@ -682,8 +641,7 @@ def _conv_wgrad_into(x, gy, gw, gbias, ks, accumulate):
     if accumulate and _DeferredWgrad.active:
         ws = x.new_empty(nbytes // 4 + 4)               # its own buffer: must survive until the batch reduce
         if not (ks == 1 and _grouped_stage1(x, (gy,), ws, (Cout,), gbias is not None)):
-            with _beside_backward(x, gy, ws):
-                K().conv2d_wgrad_partials(x, gy, ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, int(gbias is not None))
+            K().conv2d_wgrad_partials(x, gy, ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, int(gbias is not None))
         _DeferredWgrad.items.append([ws.data_ptr(), gw.data_ptr(), gbias.data_ptr() if gbias is not None else 0,
                                      B, Cin, Cout, H, W, ks, 1])
         _DeferredWgrad.keep.append((ws, gw, gbias))
@@ -701,15 +659,13 @@ def _s2_wgrad_into(mode, lo_or_x, gy, gw, gbias, B, Cin, Cout, H, W):
     nbytes = getattr(K(), name + '_wgrad_workspace')(B, Cin, Cout, H, W)
     if _DeferredWgrad.active:
         ws = gy.new_empty(nbytes // 4 + 4)               # its own buffer: must survive until the batch reduce
-        with _beside_backward(lo_or_x, gy, ws):
-            getattr(K(), name + '_wgrad_partials')(lo_or_x, gy, ws, ws.numel() * 4, B, Cin, Cout, H, W, int(gbias is not None))
+        getattr(K(), name + '_wgrad_partials')(lo_or_x, gy, ws, ws.numel() * 4, B, Cin, Cout, H, W, int(gbias is not None))
         _DeferredWgrad.s2_items.append([ws.data_ptr(), gw.data_ptr(), gbias.data_ptr() if gbias is not None else 0,
                                         B, Cin, Cout, H, W, mode, 1])
         _DeferredWgrad.keep.append((ws, gw, gbias))
         return
     ws = _ws(gy, nbytes)
-    with _beside_backward(lo_or_x, gy, ws):
-        getattr(K(), name + '_wgrad')(lo_or_x, gy, gw, ws, ws.numel() * 4, B, Cin, Cout, H, W, 1, gbias)
+    getattr(K(), name + '_wgrad')(lo_or_x, gy, gw, ws, ws.numel() * 4, B, Cin, Cout, H, W, 1, gbias)
 
 
 class _ConvWgrad(Function):
@@ -1325,7 +1281,7 @@ def _derive_known_forms(owner):
         wp = w.new_empty(4, Cin, Cout, 2, 2)
         rows.append([w.data_ptr(), w4.data_ptr(), wp.data_ptr(), Cout, Cin])
         _FilterForms.cache[(w.data_ptr(), tuple(w.shape))] = (w, w._version, w4.detach(), wp.detach())
-    K().poolconv3x3_weights_batch(torch.tensor(rows, dtype=torch.int64), len(rows))
+    K().poolconv3x3_weights_batch(*_host_rows(rows))
 
 
 def _poolconv_weights(x_like, w):

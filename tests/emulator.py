@@ -9,14 +9,21 @@ Two uses:
   * ``-m gpu``: per-kernel expected values for the HIP kernels (same call, CPU
     copies of the same inputs).
 """
+import ctypes
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 
 def _v(t, *shape):
     return t.view(*shape)
+
+
+def at(addr, n):
+    """A float32 view of host memory (the ``*_batch`` tables hold addresses; every tensor is a CPU tensor under the emulator)."""
+    return torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * n).from_address(addr)))
 
 
 class Emulator:
@@ -173,12 +180,6 @@ class Emulator:
         return 0
 
     def conv2d_wgrad_reduce_batch(self, items, n_items):
-        import ctypes
-        import numpy as np
-
-        def at(addr, n):          # a float32 view of host memory (every tensor is a CPU tensor under the emulator)
-            return torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * n).from_address(addr)))
-
         assert items.dtype == torch.int64 and tuple(items.shape) == (n_items, 10)
         for part, gw, gbias, B, Cin, Cout, H, W, ks, accumulate in items.tolist():
             E = Cout * Cin * ks * ks
@@ -210,12 +211,6 @@ class Emulator:
         return 0
 
     def s2_wgrad_reduce_batch(self, items, n_items):
-        import ctypes
-        import numpy as np
-
-        def at(addr, n):
-            return torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * n).from_address(addr)))
-
         assert items.dtype == torch.int64 and tuple(items.shape) == (n_items, 10)
         for part, gw, gbias, B, Cin, Cout, H, W, mode, accumulate in items.tolist():
             assert mode in (0, 1)
@@ -244,12 +239,6 @@ class Emulator:
         return 0
 
     def poolconv3x3_weights_batch(self, items, n_items):
-        import ctypes
-        import numpy as np
-
-        def at(addr, n):
-            return torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * n).from_address(addr)))
-
         assert items.dtype == torch.int64 and tuple(items.shape) == (n_items, 5)
         for w, w4, wp, Cout, Cin in items.tolist():
             self.poolconv3x3_weights(at(w, Cout * Cin * 9), at(w4, Cout * Cin * 16), at(wp, Cout * Cin * 16), Cout, Cin)

@@ -1,7 +1,7 @@
 """Host logic of the grouped 1x1 weight gradients on CPU: inside ``functional.deferred_wgrad()`` a 1x1 layer (and the theta / phi / g
 projections of an attention block) launches nothing at the time of the call -- its stage 1 runs in ONE
-``conv1x1_wgrad_partials_batch`` at the flush, in front of the reduce rounds.  A backend without that entry point, and
-TG_WGRAD_STREAM=1, keep the per-layer sequence of calls.  (The kernels themselves: tests/test_grouped_wgrad_gpu.py.)"""
+``conv1x1_wgrad_partials_batch`` at the flush, in front of the reduce rounds.  A backend without that entry point keeps the
+per-layer sequence of calls.  (The kernels themselves: tests/test_grouped_wgrad_gpu.py.)"""
 import pytest
 import torch
 
@@ -114,36 +114,11 @@ def test_no_per_layer_1x1_launch_inside_the_context_and_one_batch_call_per_flush
     assert TF._DeferredWgrad.keep == [] and TF._DeferredWgrad.stage1 == [] and TF._DeferredWgrad.items == []
 
 
-def _calls(log):
-    return [(name, ks, None if rows is None else tuple(rows.shape), active) for name, ks, rows, active in log]
-
-
 @pytest.mark.parametrize('phase', ['d', 'g'])
 @pytest.mark.parametrize('case', FIXTURES)
-def test_fallbacks_issue_the_old_sequence_of_calls(case, phase, monkeypatch):
+def test_fallbacks_issue_the_old_sequence_of_calls(case, phase):
     fx = load_golden(case)
     plain, plain_log = recording(Emulator)                 # a backend without the batch entry
-    want = run_phase(fx, phase, plain)
+    run_phase(fx, phase, plain)
     assert not any(name == 'conv1x1_wgrad_partials_batch' for name, *_ in plain_log)
     assert any(name == 'conv2d_wgrad_partials' and ks == 1 and active for name, ks, _, active in plain_log)
-
-    monkeypatch.setattr(TF._WgradStream, 'enabled', True)  # TG_WGRAD_STREAM=1 (read once at import)
-    em, log = recording(GroupedEmulator)
-    got = run_phase(fx, phase, em)
-    assert _calls(log) == _calls(plain_log)
-    assert torch.equal(got, want)
-
-
-def test_size_cut_off_keeps_large_layers_on_their_own_launch(monkeypatch):
-    fx = load_golden('c32_cnn_b16')
-    em, log = recording(GroupedEmulator)
-    run_phase(fx, 'd', em)
-    rows = [e for e in log if e[0] == 'conv1x1_wgrad_partials_batch'][0][2]
-    nbytes = sorted(int(4 * r[9] * r[11] * r[12] * (r[10] + r[6] + r[7] + r[8])) for r in rows.tolist())
-    assert nbytes[0] < nbytes[-1]
-    monkeypatch.setattr(TF, 'GROUPED_WGRAD_MAX_BYTES', nbytes[0])
-    em, log = recording(GroupedEmulator)
-    run_phase(fx, 'd', em)
-    kept = [e for e in log if e[0] == 'conv1x1_wgrad_partials_batch'][0][2]
-    per_layer = [e for e in log if e[0] == 'conv2d_wgrad_partials' and e[1] == 1 and e[3]]
-    assert len(kept) == nbytes.count(nbytes[0]) and len(kept) + len(per_layer) == len(rows)

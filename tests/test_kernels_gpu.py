@@ -271,6 +271,117 @@ def test_stride2_weight_gradients_in_two_steps_are_bit_identical(K, shape):
         assert torch.equal(got[2 * mode + 1][0], gw2) and torch.equal(got[2 * mode + 1][1], b0)
 
 
+def _s2_table(K, n=18):
+    """``n`` rows of tg_s2_wgrad_reduce_batch (more than the 16 one launch holds), stage 1 done: small 8x8, odd and 16x16 planes, the
+    modes alternating, with and without bias, overwriting and accumulating -> rows, [(gw, gb)], [(wanted gw, wanted gb)] from the
+    one-call forms, and what must stay alive."""
+    shapes = [(3, 5, 7, 8, 8), (2, 5, 7, 12, 10), (2, 16, 8, 16, 16)]
+    rows, got, want, keep = [], [], [], []
+    for i in range(n):
+        B, Cin, Cout, H, W = shapes[i % 3]
+        mode, with_bias, acc = i % 2, (i // 2) % 2, (i // 3) % 2
+        name = 'upconv3x3' if mode else 'poolconv3x3'
+        lo = rnd(B, Cin, *((H, W) if mode else (2 * H, 2 * W)), seed=i).cuda()
+        hi = rnd(B, Cout, *((2 * H, 2 * W) if mode else (H, W)), seed=50 + i).cuda()
+        w0, b0 = rnd(Cout, Cin, 3, 3, seed=100 + i).cuda(), rnd(Cout, seed=150 + i).cuda()
+        nbytes = getattr(K, name + '_wgrad_workspace')(B, Cin, Cout, H, W)
+        ws = workspace(nbytes).cuda()
+        a, ab = w0.clone(), b0.clone()
+        getattr(K, name + '_wgrad')(lo, hi, a, ws, ws.numel() * 4, B, Cin, Cout, H, W, acc, ab if with_bias else None)
+        want.append((a, ab))
+        ws2 = workspace(nbytes).cuda()
+        getattr(K, name + '_wgrad_partials')(lo, hi, ws2, ws2.numel() * 4, B, Cin, Cout, H, W, with_bias)
+        gw, gb = w0.clone(), b0.clone()
+        rows.append([ws2.data_ptr(), gw.data_ptr(), gb.data_ptr() if with_bias else 0, B, Cin, Cout, H, W, mode, acc])
+        got.append((gw, gb))
+        keep.append(ws2)
+    return rows, got, want, keep
+
+
+def test_stride2_batched_reduce_is_bit_identical_across_launches(K):
+    """18 rows: tg_s2_wgrad_reduce_batch cuts them into two launches (16 items per argument block); each row == its one-call form."""
+    rows, got, want, keep = _s2_table(K)
+    assert {(r[8], bool(r[2]), r[9]) for r in rows} == {(m, b, a) for m in (0, 1) for b in (False, True) for a in (0, 1)}
+    K.s2_wgrad_reduce_batch(torch.tensor(rows, dtype=torch.int64), len(rows))
+    torch.cuda.synchronize()
+    for (gw, gb), (a, ab) in zip(got, want):
+        assert torch.equal(gw, a) and torch.equal(gb, ab)
+
+
+def _forms_table(n=18):
+    """``n`` rows of tg_poolconv3x3_weights_batch: Cout*Cin below one 256-thread workgroup, no multiple of 256, and several of them."""
+    pairs = [(5, 7), (20, 18), (16, 16), (33, 40)]
+    assert 5 * 7 < 256 and (20 * 18) % 256 and (33 * 40) % 256
+    rows, ws, outs = [], [], []
+    for i in range(n):
+        Cout, Cin = pairs[i % len(pairs)]
+        w = rnd(Cout, Cin, 3, 3, seed=i).cuda()
+        w4, wp = rnd(Cout, Cin, 4, 4, seed=30 + i).cuda(), rnd(4, Cin, Cout, 2, 2, seed=60 + i).cuda()
+        rows.append([w.data_ptr(), w4.data_ptr(), wp.data_ptr(), Cout, Cin])
+        ws.append(w)
+        outs.append((w4, wp))
+    return rows, ws, outs
+
+
+def test_poolconv_weights_batch_is_bit_identical_across_launches(K):
+    """18 rows (two launches of at most 16 items) == 18 single tg_poolconv3x3_weights calls, bit for bit."""
+    rows, ws, outs = _forms_table()
+    K.poolconv3x3_weights_batch(torch.tensor(rows, dtype=torch.int64), len(rows))
+    torch.cuda.synchronize()
+    for (w, w4, wp, Cout, Cin), src, (got4, gotp) in zip(rows, ws, outs):
+        one4, onep = torch.zeros_like(got4), torch.zeros_like(gotp)
+        K.poolconv3x3_weights(src, one4, onep, Cout, Cin)
+        assert torch.equal(got4, one4) and torch.equal(gotp, onep)
+
+
+def _rejected_unwritten(call, rows, outs, code):
+    """``call(table, n)`` fails with ``code`` and no tensor of ``outs`` changed: every row is checked before the first launch."""
+    from tartangan_amd import backend
+    before = [t.clone() for t in outs]
+    torch.cuda.synchronize()
+    with pytest.raises(backend.KernelError, match=f'code {code}$'):
+        call(torch.tensor(rows, dtype=torch.int64), len(rows))
+    torch.cuda.synchronize()
+    for t, t0 in zip(outs, before):
+        assert torch.equal(t, t0)
+
+
+def test_a_bad_row_behind_the_first_launch_leaves_nothing_written(K):
+    """A table longer than one argument block whose bad row sits in the SECOND launch's share: the error comes back and not even
+    the first launch has run -- no output, no accumulating gradient has changed.  (Every address in the tables is live device
+    memory or 0.)"""
+    # tg_s2_wgrad_reduce_batch: the 17th of 18 rows without a gw (-1), then on a 4x4 plane, which the stride-2 kernels do not take (-2)
+    rows, got, _, keep = _s2_table(K)
+    outs = [t for pair in got for t in pair]
+    bad = [list(r) for r in rows]
+    bad[16][1] = 0
+    _rejected_unwritten(K.s2_wgrad_reduce_batch, bad, outs, -1)
+    bad = [list(r) for r in rows]
+    bad[16][6:8] = [4, 4]
+    _rejected_unwritten(K.s2_wgrad_reduce_batch, bad, outs, -2)
+    # tg_poolconv3x3_weights_batch: the 17th of 18 rows without a w4
+    rows, ws, forms = _forms_table()
+    rows[16][1] = 0
+    _rejected_unwritten(K.poolconv3x3_weights_batch, rows, [t for pair in forms for t in pair], -1)
+    # tg_conv2d_wgrad_reduce_batch (40 items per launch): the 41st of 45 rows without a gw, then with a 5x5 filter (-2)
+    rows, outs, keep = [], [], []
+    for i in range(45):
+        B, Cin, Cout, H, W, ks = [(3, 5, 7, 20, 12, 3), (2, 8, 4, 8, 8, 1), (2, 16, 16, 4, 4, 3)][i % 3]
+        x, gy = rnd(B, Cin, H, W, seed=i).cuda(), rnd(B, Cout, H, W, seed=100 + i).cuda()
+        ws = workspace(K.conv2d_wgrad_workspace(B, Cin, Cout, H, W, ks)).cuda()
+        K.conv2d_wgrad_partials(x, gy, ws, ws.numel() * 4, B, Cin, Cout, H, W, ks, 1)
+        gw, gb = rnd(Cout, Cin, ks, ks, seed=200 + i).cuda(), rnd(Cout, seed=300 + i).cuda()
+        rows.append([ws.data_ptr(), gw.data_ptr(), gb.data_ptr(), B, Cin, Cout, H, W, ks, i % 2])
+        outs += [gw, gb]
+        keep.append(ws)
+    bad = [list(r) for r in rows]
+    bad[40][1] = 0
+    _rejected_unwritten(K.conv2d_wgrad_reduce_batch, bad, outs, -1)
+    bad = [list(r) for r in rows]
+    bad[40][8] = 5
+    _rejected_unwritten(K.conv2d_wgrad_reduce_batch, bad, outs, -2)
+
+
 @pytest.mark.parametrize('op', ['pool_conv', 'up_conv'])
 def test_stride2_functions_under_autograd(K, op):
     """The Functions built on the stride-2 kernels, on the GPU, against plain torch on the CPU: values, first-order
