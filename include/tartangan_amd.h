@@ -178,6 +178,54 @@ int tg_poolconv3x3_wgrad_partials(const float* x, const float* gy, float* worksp
 int tg_upconv3x3_wgrad_partials(const float* a, const float* gy, float* workspace, size_t workspace_bytes, int B, int Cin, int Cout,
                                 int H, int W, int want_bias, void* stream);
 int tg_s2_wgrad_reduce_batch(const tg_host_i64* items /*host*/, int n_items, void* stream);
+/* Which kernels would a call launch?  (tg_version 109; host only like the *_supported queries: no device, no HIP call, nothing
+ * launched.)  The convolution entry points above choose among ~250 kernel instantiations by workgroup counts, channel
+ * divisibility, plane size, pointer alignment and three process-wide switches.  This query makes the REAL call of entry point
+ * `op` with made-up addresses under a thread-local probe: every launch site records instead of launching, so the answer comes
+ * from the dispatch code itself.  -> one line per launch, in order (the four phases of an up-conv, stage 1 then the reduce):
+ *     "<kernel as its demangled symbol reads, tile geometries by alias: conv_dma_kernel<GX, 32, 2, 8, false>>; <flag>=<value> ..."
+ * the flags being the host-computed path arguments of that launch (vx / vw / vg / vh / vl: 16-byte staging of an operand;
+ * swz / flags: swizzled tile order; prio: TG_DMA_PRIO; bias / res / res_up: epilogue operands present, residual at half
+ * resolution; dgrad, mode, items, *segs), and a last line "rc=<code>" if the call returned one.  The string belongs to the
+ * calling thread and lives until its next call.
+ *   op            TG_OP_* below, one per launching entry point
+ *   dims          as the entry point names them; tg_conv1x1_multi_* and _wgrad_partials_batch: c0 = Cout, c1, c2;
+ *                 tg_rgb_compose_*: (Cout, C = Cin, Cimg = ks); tg_s2_wgrad_reduce_batch: ks is the row's mode; the batch
+ *                 entries get a one-row table
+ *   unaligned     bit k set: the k-th pointer parameter (the k-th address field of a table row) sits 4 bytes off a 16-byte
+ *                 boundary; nullable pointers keep their bit
+ *                 (4 bytes is the only offset modelled: a pointer 8 bytes off -- 8- but not 16-byte aligned, which some
+ *                 stride-2 forms treat differently -- cannot be asked for, so the answers are not exhaustive over alignment)
+ *   has_bias      bias / gbias / want_bias;  has_residual: residual (tg_conv2d_fwd_up2res always has one)
+ *   wino, dma, prio   TG_CONV_WINO / TG_CONV_DMA / TG_DMA_PRIO for this call only; < 0: what the process read from its environment */
+#define TG_OP_CONV2D_FWD 0
+#define TG_OP_CONV2D_FWD_UP2RES 1
+#define TG_OP_CONV2D_DGRAD 2
+#define TG_OP_CONV2D_WGRAD 3
+#define TG_OP_CONV2D_WGRAD_PARTIALS 4
+#define TG_OP_CONV2D_WGRAD_REDUCE_BATCH 5
+#define TG_OP_CONV1X1_WGRAD_PARTIALS_BATCH 6
+#define TG_OP_UPCONV3X3_WEIGHTS 7
+#define TG_OP_UPCONV3X3_WEIGHTS_T 8
+#define TG_OP_UPCONV3X3_WEIGHTS_PAIR 9
+#define TG_OP_UPCONV3X3_FWD 10
+#define TG_OP_UPCONV3X3_DGRAD 11
+#define TG_OP_UPCONV3X3_WGRAD 12
+#define TG_OP_UPCONV3X3_WGRAD_PARTIALS 13
+#define TG_OP_POOLCONV3X3_WEIGHTS 14
+#define TG_OP_POOLCONV3X3_WEIGHTS_BATCH 15
+#define TG_OP_POOLCONV3X3_FWD 16
+#define TG_OP_POOLCONV3X3_DGRAD 17
+#define TG_OP_POOLCONV3X3_WGRAD 18
+#define TG_OP_POOLCONV3X3_WGRAD_PARTIALS 19
+#define TG_OP_S2_WGRAD_REDUCE_BATCH 20
+#define TG_OP_RGB_COMPOSE_FWD 21
+#define TG_OP_RGB_COMPOSE_BWD 22
+#define TG_OP_CONV1X1_MULTI_FWD 23
+#define TG_OP_CONV1X1_MULTI_DGRAD 24
+#define TG_OP_CONV1X1_MULTI_WGRAD 25
+const char* tg_conv_dispatch(int op, int B, int Cin, int Cout, int H, int W, int ks, int c1, int c2, int unaligned, int has_bias,
+                             int has_residual, int wino, int dma, int prio);
 /* out[c] (+)= sum_{b,p} x[b][c][p]   (linear bias grad); workspace: tg_bn_workspace(B,C,HW) bytes */
 int tg_channel_sum(const float* x, float* out, float* workspace, int B, int C, int HW, int accumulate,
                    void* stream);

@@ -16,7 +16,13 @@
     if ((v) <= 0) return TG_EINVAL; \
   } while (0)
 
+// Dispatch probe (tg_conv_dispatch, conv.hip): while this thread's probe is set, launch sites record the kernel they chose
+// instead of launching it and no HIP function is called.  Null in normal operation.
+struct TgProbe;
+inline thread_local TgProbe* tg_probe = nullptr;
+
 static inline int tg_launch_status() {
+  if (tg_probe) return TG_OK;
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? TG_OK : (int)e;
 }

@@ -19,12 +19,21 @@
 // Pixel tiles:
 //   256 pixels, waves split pixels : G4 (16 4x4 images) G8 (4 8x8) G16 (one 16x16) GX (8 rows x 32)
 //    64 pixels, waves split K       : G4k G8k G16k  -- small-spatial layers still fill the chip
+#include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <utility>
 
 #include "common.h"
 #include "grouped.h"
+
+// What tg_conv_dispatch's probe (common.h) collects: one line per launch site reached, and the call's three switches
+struct TgProbe {
+  std::string out;
+  int wino, dma, prio;         // TG_CONV_WINO / TG_CONV_DMA / TG_DMA_PRIO for this call; < 0: the process's cached value
+};
 
 namespace {
 
@@ -93,6 +102,39 @@ __device__ __forceinline__ TileCoord decode_tile(int t, int H, int W) {
   c.w0 = (rem - tr * tw_tiles) * G::TW;
   return c;
 }
+
+// ---- the one launch macro of this file.  Normally it launches; under a probe (tg_conv_dispatch) it records
+// "<kernel as its demangled symbol reads>; <host-computed path flags>" and launches nothing.  KERNEL and ARGS come in
+// parentheses (template commas); what follows them is the record's printf format and values, spelled at the launch site.
+__attribute__((format(printf, 1, 2))) static void probe_record(const char* fmt, ...) {
+  char line[256];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(line, sizeof line, fmt, ap);
+  va_end(ap);
+  tg_probe->out += line;
+  tg_probe->out += '\n';
+}
+#define TG_UNPAREN(...) __VA_ARGS__
+#define TG_LAUNCH(KERNEL, GRID, BLOCK, ST, ARGS, ...)     \
+  do {                                                    \
+    if (tg_probe) probe_record(__VA_ARGS__);              \
+    else TG_UNPAREN KERNEL<<<GRID, BLOCK, 0, ST>>> ARGS;  \
+  } while (0)
+static inline const char* tf(bool b) { return b ? "true" : "false"; }
+template <class G>
+static constexpr const char* geo_name() {
+  if constexpr (std::is_same_v<G, G4>) return "G4";
+  else if constexpr (std::is_same_v<G, G8>) return "G8";
+  else if constexpr (std::is_same_v<G, G16>) return "G16";
+  else if constexpr (std::is_same_v<G, GX>) return "GX";
+  else if constexpr (std::is_same_v<G, G4k>) return "G4k";
+  else if constexpr (std::is_same_v<G, G8k>) return "G8k";
+  else return "G16k";
+}
+// epilogue operands of the forward-type kernels: bias, residual, residual at half resolution (Shape::res_up)
+#define TG_EPI_FMT " bias=%d res=%d res_up=%d"
+#define TG_EPI_VAL bias != nullptr, residual != nullptr, s.res_up
 
 template <class G>
 static inline int num_tiles(int B, int H, int W) {
@@ -863,10 +905,12 @@ static int launch_conv1x1_direct(const float* x, const float* w, const float* bi
   const bool vec = (HW % 4 == 0) && tg_aligned16(x) && tg_aligned16(y) && (!residual || tg_aligned16(residual));
   if (vec) {
     dim3 grid((HW / 4 + 255) / 256, s.B);
-    conv1x1_direct_kernel<CO, 4><<<grid, 256, 0, st>>>(x, w, bias, residual, y, s.Cin, s.Cout, HW, w_so, w_si);
+    TG_LAUNCH((conv1x1_direct_kernel<CO, 4>), grid, 256, st, (x, w, bias, residual, y, s.Cin, s.Cout, HW, w_so, w_si),
+              "conv1x1_direct_kernel<%d, 4>; dgrad=%d bias=%d res=%d", CO, dgrad, bias != nullptr, residual != nullptr);
   } else {
     dim3 grid((HW + 255) / 256, s.B);
-    conv1x1_direct_kernel<CO, 1><<<grid, 256, 0, st>>>(x, w, bias, residual, y, s.Cin, s.Cout, HW, w_so, w_si);
+    TG_LAUNCH((conv1x1_direct_kernel<CO, 1>), grid, 256, st, (x, w, bias, residual, y, s.Cin, s.Cout, HW, w_so, w_si),
+              "conv1x1_direct_kernel<%d, 1>; dgrad=%d bias=%d res=%d", CO, dgrad, bias != nullptr, residual != nullptr);
   }
   return tg_launch_status();
 }
@@ -987,7 +1031,10 @@ static int launch_conv1x1_segs(ChanSegs xs, const float* w, const float* bias, c
   const int w_so = dgrad ? 1 : s.Cin, w_si = dgrad ? s.Cout : 1;      // (as launch_conv1x1_direct)
   const unsigned grid = (unsigned)((quads + 63) / 64);                 // 4 waves x 16 quads per workgroup
   const int nco = (s.Cout + 15) / 16;
-#define TG_1X1(N) conv1x1_mfma_kernel<N><<<grid, 256, 0, st>>>(xs, w, bias, residual, ys, s.Cin, s.Cout, HW, quads, w_so, w_si)
+#define TG_1X1(N)                                                                                                              \
+  TG_LAUNCH((conv1x1_mfma_kernel<N>), grid, 256, st, (xs, w, bias, residual, ys, s.Cin, s.Cout, HW, quads, w_so, w_si),        \
+            "conv1x1_mfma_kernel<%d>; dgrad=%d bias=%d res=%d xsegs=%d ysegs=%d", N, dgrad, bias != nullptr, residual != nullptr, \
+            xs.start[1] < s.Cin ? 3 : 1, ys.start[1] < s.Cout ? 3 : 1)
   if (nco <= 1) TG_1X1(1);
   else if (nco == 2) TG_1X1(2);
   else if (nco <= 4) TG_1X1(4);
@@ -1480,10 +1527,14 @@ static int launch_conv1x1_wgrad_segs(const float* x, ChanSegs gy, float* part, f
   const int64_t groups = (int64_t)s.B * (HW / 16);
   const int mt = conv1x1_wgrad_mt(s.Cout), nt = conv1x1_wgrad_nt(s.Cin);
   dim3 grid(S, (s.Cout + 16 * mt - 1) / (16 * mt), (s.Cin + 16 * nt - 1) / (16 * nt));
-  if (mt == 1 && nt == 1) conv1x1_wgrad_stream_kernel<1, 1><<<grid, 256, 0, st>>>(x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S);
-  else if (mt == 1) conv1x1_wgrad_stream_kernel<1, 2><<<grid, 256, 0, st>>>(x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S);
-  else if (nt == 1) conv1x1_wgrad_stream_kernel<2, 1><<<grid, 256, 0, st>>>(x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S);
-  else conv1x1_wgrad_stream_kernel<2, 2><<<grid, 256, 0, st>>>(x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S);
+#define TG_WG1_ARGS (x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S)
+#define TG_WG1_FMT " bias=%d gysegs=%d", bias_part != nullptr, gy.start[1] < s.Cout ? 3 : 1
+  if (mt == 1 && nt == 1) TG_LAUNCH((conv1x1_wgrad_stream_kernel<1, 1>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<1, 1>;" TG_WG1_FMT);
+  else if (mt == 1) TG_LAUNCH((conv1x1_wgrad_stream_kernel<1, 2>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<1, 2>;" TG_WG1_FMT);
+  else if (nt == 1) TG_LAUNCH((conv1x1_wgrad_stream_kernel<2, 1>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<2, 1>;" TG_WG1_FMT);
+  else TG_LAUNCH((conv1x1_wgrad_stream_kernel<2, 2>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<2, 2>;" TG_WG1_FMT);
+#undef TG_WG1_ARGS
+#undef TG_WG1_FMT
   return tg_launch_status();
 }
 static int launch_conv1x1_wgrad_stream(const float* x, const float* gy, float* part, float* bias_part, Shape s, int S, hipStream_t st) {
@@ -2697,12 +2748,17 @@ static inline int plane_vec_ok(const void* p, int W) { return (W % 4 == 0) && tg
 // stride-2 family: low-resolution planes of 8x8 (4 images per tile), 16x16 and larger; workgroups needed to pay off
 static inline bool s2_geo(GeoId g) { return g == GEO_8 || g == GEO_16 || g == GEO_X; }
 static inline int64_t s2_min_wgs(GeoId g) { return g == GEO_8 ? 128 : 256; }
-#define TG_S2_DISPATCH(g, KERNEL, ...)                                                   \
-  do {                                                                                   \
-    if ((g) == GEO_8) KERNEL<G8><<<grid, CT_THREADS, 0, st>>>(__VA_ARGS__);              \
-    else if ((g) == GEO_16) KERNEL<G16><<<grid, CT_THREADS, 0, st>>>(__VA_ARGS__);       \
-    else KERNEL<GX><<<grid, CT_THREADS, 0, st>>>(__VA_ARGS__);                           \
+// (ARGS in parentheses; after them the flags part of the probe's record, see TG_LAUNCH)
+#define TG_S2_DISPATCH(g, KERNEL, ARGS, ...)                                                                          \
+  do {                                                                                                                \
+    if ((g) == GEO_8) TG_LAUNCH((KERNEL<G8>), grid, CT_THREADS, st, ARGS, #KERNEL "<G8>;" __VA_ARGS__);               \
+    else if ((g) == GEO_16) TG_LAUNCH((KERNEL<G16>), grid, CT_THREADS, st, ARGS, #KERNEL "<G16>;" __VA_ARGS__);       \
+    else TG_LAUNCH((KERNEL<GX>), grid, CT_THREADS, st, ARGS, #KERNEL "<GX>;" __VA_ARGS__);                            \
   } while (0)
+
+// records of the four stride-2 forward-type families: LDS-DMA staged (`t` tiles in scope) / register staged
+#define TG_S2D_REC " swz=%d prio=%d bias=%d res=%d", t % 8 == 0, s.prio, bias != nullptr, residual != nullptr
+#define TG_S2R_REC " vx=%d vw=%d bias=%d res=%d", vx, vw, bias != nullptr, residual != nullptr
 
 // stride-2 transpose form: 8x8 planes that give fewer than 256 four-image tiles run as single-image K-split tiles
 static bool s2_dma_ok(const void* x, const void* w, const Shape& s, int hi_channels);
@@ -2723,13 +2779,15 @@ static bool try_launch_poolwino(const float* x, const float* w4, const float* bi
   if (Hh % 8 == 0 && Wh % 32 == 0) {
     const int tiles = num_tiles<GX>(s.B, Hh, Wh);
     if ((int64_t)tiles * cob < min_wgs) return false;
-    conv_poolwino_dma_kernel<GX, 2><<<dim3(tiles, cob), CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, (tiles % 8 == 0) ? 1 : 0);
+    TG_LAUNCH((conv_poolwino_dma_kernel<GX, 2>), dim3(tiles, cob), CT_THREADS, st, (x, w4, bias, residual, y, s, (tiles % 8 == 0) ? 1 : 0),
+              "conv_poolwino_dma_kernel<GX, 2>; flags=%d bias=%d res=%d", (tiles % 8 == 0) ? 1 : 0, bias != nullptr, residual != nullptr);
     return true;
   }
   if (Hh == 16 && Wh == 16) {
     const int tiles = num_tiles<G16>(s.B, Hh, Wh);
     if ((int64_t)tiles * cob < min_wgs) return false;
-    conv_poolwino_dma_kernel<G16, 2><<<dim3(tiles, cob), CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, (tiles % 8 == 0) ? 1 : 0);
+    TG_LAUNCH((conv_poolwino_dma_kernel<G16, 2>), dim3(tiles, cob), CT_THREADS, st, (x, w4, bias, residual, y, s, (tiles % 8 == 0) ? 1 : 0),
+              "conv_poolwino_dma_kernel<G16, 2>; flags=%d bias=%d res=%d", (tiles % 8 == 0) ? 1 : 0, bias != nullptr, residual != nullptr);
     return true;
   }
   return false;
@@ -2743,24 +2801,32 @@ static void launch_upT(GeoId g, const float* x, const float* w4, const float* bi
     s.prio = dma_prio();
     if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
       const int t = num_tiles<G8k>(s.B, s.H, s.W);
-      conv_upT_dma_kernel<G8k, true><<<dim3(t, cot), CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
+      TG_LAUNCH((conv_upT_dma_kernel<G8k, true>), dim3(t, cot), CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
+                "conv_upT_dma_kernel<G8k, true>;" TG_S2D_REC);
       return;
     }
     const int t = geo_tiles(g, s.B, s.H, s.W);
     dim3 grid(t, cot);
-    if (g == GEO_8) conv_upT_dma_kernel<G8, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
-    else if (g == GEO_16) conv_upT_dma_kernel<G16, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
-    else conv_upT_dma_kernel<GX, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, t % 8 == 0);
+    if (g == GEO_8) TG_LAUNCH((conv_upT_dma_kernel<G8, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
+                              "conv_upT_dma_kernel<G8, false>;" TG_S2D_REC);
+    else if (g == GEO_16) TG_LAUNCH((conv_upT_dma_kernel<G16, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
+                                    "conv_upT_dma_kernel<G16, false>;" TG_S2D_REC);
+    else TG_LAUNCH((conv_upT_dma_kernel<GX, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
+                   "conv_upT_dma_kernel<GX, false>;" TG_S2D_REC);
     return;
   }
   if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
-    conv_upT_kernel<G8k, true><<<dim3(num_tiles<G8k>(s.B, s.H, s.W), cot), CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, vx, vw);
+    TG_LAUNCH((conv_upT_kernel<G8k, true>), dim3(num_tiles<G8k>(s.B, s.H, s.W), cot), CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
+              "conv_upT_kernel<G8k, true>;" TG_S2R_REC);
     return;
   }
   dim3 grid(geo_tiles(g, s.B, s.H, s.W), cot);
-  if (g == GEO_8) conv_upT_kernel<G8, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, vx, vw);
-  else if (g == GEO_16) conv_upT_kernel<G16, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, vx, vw);
-  else conv_upT_kernel<GX, false><<<grid, CT_THREADS, 0, st>>>(x, w4, bias, residual, y, s, vx, vw);
+  if (g == GEO_8) TG_LAUNCH((conv_upT_kernel<G8, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
+                            "conv_upT_kernel<G8, false>;" TG_S2R_REC);
+  else if (g == GEO_16) TG_LAUNCH((conv_upT_kernel<G16, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
+                                  "conv_upT_kernel<G16, false>;" TG_S2R_REC);
+  else TG_LAUNCH((conv_upT_kernel<GX, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
+                 "conv_upT_kernel<GX, false>;" TG_S2R_REC);
 }
 
 static void launch_upfwd(GeoId g, const float* x, const float* wp, const float* bias, const float* residual, float* y, Shape s,
@@ -2770,24 +2836,32 @@ static void launch_upfwd(GeoId g, const float* x, const float* wp, const float* 
     s.prio = dma_prio();
     if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
       const int t = num_tiles<G8k>(s.B, s.H, s.W);
-      conv_upfwd_dma_kernel<G8k, true><<<dim3(t, cot), CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
+      TG_LAUNCH((conv_upfwd_dma_kernel<G8k, true>), dim3(t, cot), CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
+                "conv_upfwd_dma_kernel<G8k, true>;" TG_S2D_REC);
       return;
     }
     const int t = geo_tiles(g, s.B, s.H, s.W);
     dim3 grid(t, cot);
-    if (g == GEO_8) conv_upfwd_dma_kernel<G8, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
-    else if (g == GEO_16) conv_upfwd_dma_kernel<G16, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
-    else conv_upfwd_dma_kernel<GX, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, t % 8 == 0);
+    if (g == GEO_8) TG_LAUNCH((conv_upfwd_dma_kernel<G8, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
+                              "conv_upfwd_dma_kernel<G8, false>;" TG_S2D_REC);
+    else if (g == GEO_16) TG_LAUNCH((conv_upfwd_dma_kernel<G16, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
+                                    "conv_upfwd_dma_kernel<G16, false>;" TG_S2D_REC);
+    else TG_LAUNCH((conv_upfwd_dma_kernel<GX, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
+                   "conv_upfwd_dma_kernel<GX, false>;" TG_S2D_REC);
     return;
   }
   if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
-    conv_upfwd_kernel<G8k, true><<<dim3(num_tiles<G8k>(s.B, s.H, s.W), cot), CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, vx, vw);
+    TG_LAUNCH((conv_upfwd_kernel<G8k, true>), dim3(num_tiles<G8k>(s.B, s.H, s.W), cot), CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
+              "conv_upfwd_kernel<G8k, true>;" TG_S2R_REC);
     return;
   }
   dim3 grid(geo_tiles(g, s.B, s.H, s.W), cot);
-  if (g == GEO_8) conv_upfwd_kernel<G8, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, vx, vw);
-  else if (g == GEO_16) conv_upfwd_kernel<G16, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, vx, vw);
-  else conv_upfwd_kernel<GX, false><<<grid, CT_THREADS, 0, st>>>(x, wp, bias, residual, y, s, vx, vw);
+  if (g == GEO_8) TG_LAUNCH((conv_upfwd_kernel<G8, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
+                            "conv_upfwd_kernel<G8, false>;" TG_S2R_REC);
+  else if (g == GEO_16) TG_LAUNCH((conv_upfwd_kernel<G16, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
+                                  "conv_upfwd_kernel<G16, false>;" TG_S2R_REC);
+  else TG_LAUNCH((conv_upfwd_kernel<GX, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
+                 "conv_upfwd_kernel<GX, false>;" TG_S2R_REC);
 }
 
 template <class G, int KS, bool DGRAD>
@@ -2799,41 +2873,46 @@ int launch_fwd_geo(const float* x, const float* w, const float* bias, const floa
   const int vw = tg_aligned16(w) && ((DGRAD ? s.Cout : s.Cin) % 4 == 0);
   // MFMA flavour: 32x32x2 when the output-channel count fills (or nearly fills) 32-row tiles, else 16x16x4
   const bool use32 = (s.Cout % 32 == 0) || s.Cout > 48;
+#define TG_FWD(MF, MT)                                                                                                    \
+  TG_LAUNCH((conv_fwd_kernel<G, KS, MF, MT, DGRAD>), grid, CT_THREADS, st, (x, w, bias, residual, y, s, vx, vw),          \
+            "conv_fwd_kernel<%s, %d, " #MF ", " #MT ", %s>; vx=%d vw=%d" TG_EPI_FMT, geo_name<G>(), KS, tf(DGRAD), vx, vw, TG_EPI_VAL)
   if (use32) {
     bool done = false;
     if constexpr (!WK) {
       // 64-channel tiles halve the patch re-reads but also the workgroup count: only when the grid stays full
       if (s.Cout > 32 && (int64_t)tiles * ((s.Cout + 63) / 64) >= 768) {
         dim3 grid(tiles, (s.Cout + 63) / 64);
-        conv_fwd_kernel<G, KS, 32, 2, DGRAD><<<grid, CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, vx, vw);
+        TG_FWD(32, 2);
         done = true;
       }
     }
     if (!done) {
       dim3 grid(tiles, (s.Cout + 31) / 32);
-      conv_fwd_kernel<G, KS, 32, 1, DGRAD><<<grid, CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, vx, vw);
+      TG_FWD(32, 1);
     }
   } else {
     if (s.Cout > 16) {
       dim3 grid(tiles, (s.Cout + 31) / 32);
-      conv_fwd_kernel<G, KS, 16, 2, DGRAD><<<grid, CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, vx, vw);
+      TG_FWD(16, 2);
     } else {
       dim3 grid(tiles, 1);
-      conv_fwd_kernel<G, KS, 16, 1, DGRAD><<<grid, CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, vx, vw);
+      TG_FWD(16, 1);
     }
   }
+#undef TG_FWD
   return tg_launch_status();
 }
 
 // ---- LDS-DMA kernel dispatch.  Two switches, read once from the environment: TG_CONV_DMA=0 sends every launch to the
 // register-staged kernels (the tests use it to reach them at small shapes), TG_DMA_PRIO=1 see conv_dma_kernel.
+// (A probe -- tg_conv_dispatch -- may carry its own value of each switch, for its call only.)
 static bool dma_enabled() {
   static const bool v = [] { const char* e = getenv("TG_CONV_DMA"); return !e || atoi(e) != 0; }();
-  return v;
+  return (tg_probe && tg_probe->dma >= 0) ? tg_probe->dma != 0 : v;
 }
 static int dma_prio() {
   static const int v = [] { const char* e = getenv("TG_DMA_PRIO"); return e ? atoi(e) : 0; }();
-  return v;
+  return (tg_probe && tg_probe->prio >= 0) ? tg_probe->prio : v;
 }
 
 // stride-2 kernels: whole 16-byte chunks (the callers checked plane / filter alignment), channel counts that keep filter rows
@@ -2846,6 +2925,12 @@ static bool s2_dma_ok(const void* x, const void* w, const Shape& s, int hi_chann
   return s.W % 4 == 0 || hi_channels;        // low-resolution rows of whole chunks (high-resolution rows: 2 W, the caller's vx)
 }
 
+// (G, DGRAD, the operands, `s` and `swz` -- bit 0: swizzled tile order, bit 5: TG_DMA_PRIO -- of the enclosing function)
+#define TG_DMA(MF, MT, CK_, GRID)                                                                                                   \
+  TG_LAUNCH((conv_dma_kernel<G, MF, MT, CK_, DGRAD>), GRID, CT_THREADS, st, (x, w, bias, residual, y, s, swz),                        \
+            "conv_dma_kernel<%s, " #MF ", " #MT ", %d, %s>; swz=%d prio=%d" TG_EPI_FMT, geo_name<G>(), CK_, tf(DGRAD), swz & 1, swz >> 5, \
+            TG_EPI_VAL)
+
 template <class G, int CK, bool DGRAD>
 static bool launch_dma_geo(const float* x, const float* w, const float* bias, const float* residual, float* y, Shape s, hipStream_t st) {
   const int64_t tiles = num_tiles<G>(s.B, s.H, s.W);
@@ -2853,11 +2938,11 @@ static bool launch_dma_geo(const float* x, const float* w, const float* bias, co
   const bool use32 = (s.Cout % 32 == 0) || s.Cout > 48;
   // output-channel tile: as wide as the grid allows (one workgroup per CU at the very least)
   if (use32 && s.Cout > 32 && tiles * ((s.Cout + 63) / 64) >= 512) {
-    conv_dma_kernel<G, 32, 2, CK, DGRAD><<<dim3(tiles, (s.Cout + 63) / 64), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
+    TG_DMA(32, 2, CK, dim3(tiles, (s.Cout + 63) / 64));
   } else if (use32 && tiles * ((s.Cout + 31) / 32) >= 256) {
-    conv_dma_kernel<G, 32, 1, CK, DGRAD><<<dim3(tiles, (s.Cout + 31) / 32), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
+    TG_DMA(32, 1, CK, dim3(tiles, (s.Cout + 31) / 32));
   } else if (tiles * ((s.Cout + 15) / 16) >= 192) {
-    conv_dma_kernel<G, 16, 1, CK, DGRAD><<<dim3(tiles, (s.Cout + 15) / 16), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
+    TG_DMA(16, 1, CK, dim3(tiles, (s.Cout + 15) / 16));
   } else {
     return false;                      // too few tiles: the K-split variants of conv_fwd_kernel fill the chip better
   }
@@ -2872,9 +2957,9 @@ static bool launch_dma_ksplit(const float* x, const float* w, const float* bias,
   // overlaps a workgroup's DMA waits, and twice as many 16-channel workgroups win (batch 64: 128->128 @4^2 15.9 -> 10.6 us,
   // 64->128 @8^2 dgrad 15.5 -> 10.2 us, 128->128 @8^2 16.6 -> 16.0 us; 256->256 @8^2, 512 workgroups, stays on 32)
   if ((s.Cout % 32 == 0 || s.Cout > 48) && tiles * ((s.Cout + 31) / 32) > 256)
-    conv_dma_kernel<G, 32, 1, 16, DGRAD><<<dim3(tiles, (s.Cout + 31) / 32), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
+    TG_DMA(32, 1, 16, dim3(tiles, (s.Cout + 31) / 32));
   else
-    conv_dma_kernel<G, 16, 1, 16, DGRAD><<<dim3(tiles, (s.Cout + 15) / 16), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, swz);
+    TG_DMA(16, 1, 16, dim3(tiles, (s.Cout + 15) / 16));
   return true;
 }
 
@@ -2908,8 +2993,14 @@ static bool try_launch_dma(const float* x, const float* w, const float* bias, co
 // only the launches that fill the chip: 64-tile workgroups on 8x8 / 4x4 planes give too few workgroups at the step's batch.
 static int wino_mode() {
   static const int v = [] { const char* e = getenv("TG_CONV_WINO"); return e ? atoi(e) : 1; }();
-  return v;
+  return (tg_probe && tg_probe->wino >= 0) ? tg_probe->wino : v;
 }
+// (G, DGRAD, the operands, `s` and `flags` -- bit 0: swizzled tile order -- of the enclosing function)
+#define TG_WINO(NB, CK_, KSPLIT, GRID)                                                                                           \
+  TG_LAUNCH((conv_wino_dma_kernel<G, NB, DGRAD, CK_, KSPLIT>), GRID, CT_THREADS, st, (x, w, bias, residual, y, s, flags),           \
+            "conv_wino_dma_kernel<%s, " #NB ", %s, %d, " #KSPLIT ">; flags=%d" TG_EPI_FMT, geo_name<G>(), tf(DGRAD), CK_, flags, \
+            TG_EPI_VAL)
+
 template <class G, bool DGRAD>
 static int launch_wino_geo(const float* x, const float* w, const float* bias, const float* residual, float* y, Shape s, hipStream_t st,
                            int64_t min_wgs) {
@@ -2917,13 +3008,13 @@ static int launch_wino_geo(const float* x, const float* w, const float* bias, co
   const int flags = (tiles % 8 == 0) ? 1 : 0;
   if (s.Cin == 4) {                      // the composed from-RGB layer: one 4-channel chunk
     if (s.Cout > 16 || (int64_t)tiles < min_wgs) return -1;
-    conv_wino_dma_kernel<G, 1, DGRAD, 4><<<dim3(tiles, 1), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, flags);
+    TG_WINO(1, 4, false, dim3(tiles, 1));
     return tg_launch_status();
   }
   if (s.Cout > 16 && (int64_t)tiles * ((s.Cout + 31) / 32) >= min_wgs)
-    conv_wino_dma_kernel<G, 2, DGRAD><<<dim3(tiles, (s.Cout + 31) / 32), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, flags);
+    TG_WINO(2, WINO_CK, false, dim3(tiles, (s.Cout + 31) / 32));
   else if ((int64_t)tiles * ((s.Cout + 15) / 16) >= min_wgs)
-    conv_wino_dma_kernel<G, 1, DGRAD><<<dim3(tiles, (s.Cout + 15) / 16), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, flags);
+    TG_WINO(1, WINO_CK, false, dim3(tiles, (s.Cout + 15) / 16));
   else
     return -1;
   return tg_launch_status();
@@ -2936,9 +3027,9 @@ static int launch_wino_ksplit(const float* x, const float* w, const float* bias,
   const int tiles = num_tiles<G>(s.B, s.H, s.W);
   const int flags = (tiles % 8 == 0) ? 1 : 0;
   if (s.Cout > 16 && (int64_t)tiles * ((s.Cout + 31) / 32) >= 256 && s.B % 2 == 0)
-    conv_wino_dma_kernel<G, 2, DGRAD, 16, true><<<dim3(tiles, (s.Cout + 31) / 32), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, flags);
+    TG_WINO(2, 16, true, dim3(tiles, (s.Cout + 31) / 32));
   else if ((int64_t)tiles * ((s.Cout + 15) / 16) >= min_wgs)
-    conv_wino_dma_kernel<G, 1, DGRAD, 16, true><<<dim3(tiles, (s.Cout + 15) / 16), CT_THREADS, 0, st>>>(x, w, bias, residual, y, s, flags);
+    TG_WINO(1, 16, true, dim3(tiles, (s.Cout + 15) / 16));
   else
     return -1;
   return tg_launch_status();
@@ -3023,6 +3114,12 @@ template <class G, int KS>
 int launch_wgrad_geo(const float* x, const float* gy, float* part, float* bias_part, Shape s, const WgPlan& p, hipStream_t st) {
   dim3 grid(p.S, p.co_tiles, p.ci_chunks);
   const int vx = plane_vec_ok(x, s.W), vg = plane_vec_ok(gy, s.W);
+#define TG_WGD(MTW, CKW_)                                                                                                  \
+  TG_LAUNCH((conv_wgrad_dma_kernel<G, MTW, CKW_>), grid, CT_THREADS, st, (x, gy, part, bias_part, s, p.tiles, p.S),          \
+            "conv_wgrad_dma_kernel<%s, " #MTW ", %d>; prio=%d bias=%d", geo_name<G>(), CKW_, s.prio, bias_part != nullptr)
+#define TG_WG(MTW)                                                                                                         \
+  TG_LAUNCH((conv_wgrad_kernel<G, KS, MTW>), grid, CT_THREADS, st, (x, gy, part, bias_part, s, p.tiles, p.S, vx, vg),        \
+            "conv_wgrad_kernel<%s, %d, " #MTW ">; vx=%d vg=%d bias=%d", geo_name<G>(), KS, vx, vg, bias_part != nullptr)
   if constexpr (KS == 3 && G::NPIX == 256) {
     // LDS-DMA staging: needs whole 16-byte chunks (W % 4, aligned planes) and 32-bit buffer offsets
     const bool small = (int64_t)s.B * (s.Cin > s.Cout ? s.Cin : s.Cout) * s.H * s.W * 4 < (1ll << 31);
@@ -3034,17 +3131,17 @@ int launch_wgrad_geo(const float* x, const float* gy, float* part, float* bias_p
       // shape of the 128 px step, they halve the workgroups per CU)
       if (s.Cin <= 4 && p.mtw == 1) {
         // the composed from-RGB layer (3 image channels + the bias channel): 36 (ci, tap) columns, not 144
-        conv_wgrad_dma_kernel<G, 1, 4><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
+        TG_WGD(1, 4);
         return tg_launch_status();
       }
       if (p.mtw == 2) {
         if constexpr (buf2 <= 160 * 1024) {
-          conv_wgrad_dma_kernel<G, 2, CKW><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
+          TG_WGD(2, CKW);
           return tg_launch_status();
         }
       } else {
         if constexpr (buf1 <= 160 * 1024) {
-          conv_wgrad_dma_kernel<G, 1, CKW><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S);
+          TG_WGD(1, CKW);
           return tg_launch_status();
         }
       }
@@ -3053,8 +3150,10 @@ int launch_wgrad_geo(const float* x, const float* gy, float* part, float* bias_p
   if constexpr (KS == 1) {
     if (conv1x1_wgrad_stream_ok(x, gy, s)) return launch_conv1x1_wgrad_stream(x, gy, part, bias_part, s, p.S, st);
   }
-  if (p.mtw == 2) conv_wgrad_kernel<G, KS, 2><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S, vx, vg);
-  else conv_wgrad_kernel<G, KS, 1><<<grid, CT_THREADS, 0, st>>>(x, gy, part, bias_part, s, p.tiles, p.S, vx, vg);
+  if (p.mtw == 2) TG_WG(2);
+  else TG_WG(1);
+#undef TG_WGD
+#undef TG_WG
   return tg_launch_status();
 }
 
@@ -3106,7 +3205,7 @@ int tg_conv2d_fwd_up2res(const float* x, const float* w, const float* bias, cons
 int tg_upconv3x3_weights(const float* w, float* wp, int Cout, int Cin, void* stream) {
   TG_CHECK_PTR(w); TG_CHECK_PTR(wp); TG_CHECK_POS(Cout); TG_CHECK_POS(Cin);
   const int n = Cout * Cin;
-  upconv_weights_kernel<<<(n + 255) / 256, 256, 0, tg_stream(stream)>>>(w, wp, n);
+  TG_LAUNCH((upconv_weights_kernel), (n + 255) / 256, 256, tg_stream(stream), (w, wp, n), "upconv_weights_kernel;");
   return tg_launch_status();
 }
 
@@ -3139,13 +3238,13 @@ int tg_upconv3x3_fwd(const float* a, const float* wp, const float* bias, const f
 
 int tg_upconv3x3_weights_t(const float* w, float* w4t, int Cout, int Cin, void* stream) {
   TG_CHECK_PTR(w); TG_CHECK_PTR(w4t); TG_CHECK_POS(Cout); TG_CHECK_POS(Cin);
-  upconvT_weights_kernel<<<(Cout * Cin + 255) / 256, 256, 0, tg_stream(stream)>>>(w, w4t, Cout, Cin);
+  TG_LAUNCH((upconvT_weights_kernel), (Cout * Cin + 255) / 256, 256, tg_stream(stream), (w, w4t, Cout, Cin), "upconvT_weights_kernel;");
   return tg_launch_status();
 }
 
 int tg_upconv3x3_weights_pair(const float* w, float* wp, float* w4t, int Cout, int Cin, void* stream) {
   TG_CHECK_PTR(w); TG_CHECK_PTR(wp); TG_CHECK_PTR(w4t); TG_CHECK_POS(Cout); TG_CHECK_POS(Cin);
-  upconv_weights_pair_kernel<<<(Cout * Cin + 255) / 256, 256, 0, tg_stream(stream)>>>(w, wp, w4t, Cout, Cin);
+  TG_LAUNCH((upconv_weights_pair_kernel), (Cout * Cin + 255) / 256, 256, tg_stream(stream), (w, wp, w4t, Cout, Cin), "upconv_weights_pair_kernel;");
   return tg_launch_status();
 }
 
@@ -3204,9 +3303,9 @@ static int s2_wgrad_stage1(const float* hi, const float* lo, float* ws, size_t w
   const int vh = plane_vec_ok(hi, 2 * W), vl = plane_vec_ok(lo, W);
   if (vh && vl && dma_enabled() && (int64_t)B * (Chi > Clo ? Chi : Clo) * H * W * 16 < (1ll << 31)) {
     s.prio = dma_prio();
-    TG_S2_DISPATCH(g, conv_wgrad_s2_dma_kernel, hi, lo, ws, s, tiles, S, bias_part, mode);
+    TG_S2_DISPATCH(g, conv_wgrad_s2_dma_kernel, (hi, lo, ws, s, tiles, S, bias_part, mode), " prio=%d bias=%d mode=%d", s.prio, bias_part != nullptr, mode);
   } else {
-    TG_S2_DISPATCH(g, conv_wgrad_s2_kernel, hi, lo, ws, s, tiles, S, vh, vl, bias_part, mode);
+    TG_S2_DISPATCH(g, conv_wgrad_s2_kernel, (hi, lo, ws, s, tiles, S, vh, vl, bias_part, mode), " vh=%d vl=%d bias=%d mode=%d", vh, vl, bias_part != nullptr, mode);
   }
   return tg_launch_status();
 }
@@ -3224,8 +3323,9 @@ static int s2_wgrad(const float* hi, const float* lo, float* gw, float* gbias, f
                     int W, int Cout, int Cin, int mode, int accumulate, hipStream_t st) {
   if (int rc = s2_wgrad_stage1(hi, lo, ws, ws_bytes, B, Clo, Chi, H, W, mode, gbias != nullptr, st)) return rc;
   const FoldItem it = s2_fold_item(ws, gw, gbias, B, Clo, Chi, H, W, Cout, Cin, mode, accumulate);
-  s2wgrad_reduce_fold_kernel<<<it.pair_blocks + (gbias ? (Cout + 3) / 4 : 0), 256, 0, st>>>(it.part, gw, it.S, Clo, Chi, Cout, Cin, mode,
-                                                                                         accumulate, it.bias_part, gbias, it.pair_blocks);
+  TG_LAUNCH((s2wgrad_reduce_fold_kernel), it.pair_blocks + (gbias ? (Cout + 3) / 4 : 0), 256, st,
+            (it.part, gw, it.S, Clo, Chi, Cout, Cin, mode, accumulate, it.bias_part, gbias, it.pair_blocks),
+            "s2wgrad_reduce_fold_kernel; bias=%d mode=%d", gbias != nullptr, mode);
   return tg_launch_status();
 }
 
@@ -3256,7 +3356,7 @@ int tg_s2_wgrad_reduce_batch(const tg_host_i64* items, int n_items, void* stream
                           mode == 0 ? Cout : Cin, mode == 0 ? Cin : Cout, H, W, Cout, Cin, mode, (int)it[9]);
         return (int64_t)f->pair_blocks + (f->gbias ? (Cout + 3) / 4 : 0);
       },
-      [st](const FoldBatch& fb, unsigned blocks) { s2wgrad_reduce_fold_batch_kernel<<<blocks, 256, 0, st>>>(fb); });
+      [st](const FoldBatch& fb, unsigned blocks) { TG_LAUNCH((s2wgrad_reduce_fold_batch_kernel), blocks, 256, st, (fb), "s2wgrad_reduce_fold_batch_kernel; items=%d", fb.n); });
 }
 
 size_t tg_poolconv3x3_wgrad_workspace(int B, int Cin, int Cout, int H, int W) {
@@ -3281,7 +3381,7 @@ int tg_upconv3x3_wgrad(const float* a, const float* gy, float* gw, float* worksp
 int tg_rgb_compose_fwd(const float* w1, const float* b1, const float* w3, float* wc, int Cout, int C, int Cimg, void* stream) {
   TG_CHECK_PTR(w1); TG_CHECK_PTR(b1); TG_CHECK_PTR(w3); TG_CHECK_PTR(wc); TG_CHECK_POS(Cout); TG_CHECK_POS(C); TG_CHECK_POS(Cimg);
   const int n = Cout * (Cimg + 1) * 9;
-  rgb_compose_fwd_kernel<<<(n + 255) / 256, 256, 0, tg_stream(stream)>>>(w1, b1, w3, wc, Cout, C, Cimg);
+  TG_LAUNCH((rgb_compose_fwd_kernel), (n + 255) / 256, 256, tg_stream(stream), (w1, b1, w3, wc, Cout, C, Cimg), "rgb_compose_fwd_kernel;");
   return tg_launch_status();
 }
 int tg_rgb_compose_bwd(const float* gwc, const float* w1, const float* b1, const float* w3, float* gw1, float* gb1, float* gw3, int Cout,
@@ -3289,7 +3389,8 @@ int tg_rgb_compose_bwd(const float* gwc, const float* w1, const float* b1, const
   TG_CHECK_PTR(gwc); TG_CHECK_PTR(w1); TG_CHECK_PTR(b1); TG_CHECK_PTR(w3); TG_CHECK_PTR(gw1); TG_CHECK_PTR(gb1); TG_CHECK_PTR(gw3);
   TG_CHECK_POS(Cout); TG_CHECK_POS(C); TG_CHECK_POS(Cimg);
   const int n = Cout * C * 9 + C * (Cimg + 1);
-  rgb_compose_bwd_kernel<<<(n + 255) / 256, 256, 0, tg_stream(stream)>>>(gwc, w1, b1, w3, gw1, gb1, gw3, Cout, C, Cimg, accumulate);
+  TG_LAUNCH((rgb_compose_bwd_kernel), (n + 255) / 256, 256, tg_stream(stream), (gwc, w1, b1, w3, gw1, gb1, gw3, Cout, C, Cimg, accumulate),
+            "rgb_compose_bwd_kernel;");
   return tg_launch_status();
 }
 
@@ -3305,12 +3406,12 @@ int tg_poolconv3x3_weights_batch(const tg_host_i64* items, int n_items, void* st
         *f = FormItem{reinterpret_cast<const float*>(it[0]), reinterpret_cast<float*>(it[1]), reinterpret_cast<float*>(it[2]), Cout, Cin};
         return (int64_t)((Cout * Cin + 255) / 256);
       },
-      [st](const FormBatch& fb, unsigned blocks) { poolconv_weights_batch_kernel<<<blocks, 256, 0, st>>>(fb); });
+      [st](const FormBatch& fb, unsigned blocks) { TG_LAUNCH((poolconv_weights_batch_kernel), blocks, 256, st, (fb), "poolconv_weights_batch_kernel; items=%d", fb.n); });
 }
 
 int tg_poolconv3x3_weights(const float* w, float* w4, float* wp, int Cout, int Cin, void* stream) {
   TG_CHECK_PTR(w); TG_CHECK_PTR(w4); TG_CHECK_PTR(wp); TG_CHECK_POS(Cout); TG_CHECK_POS(Cin);
-  poolconv_weights_kernel<<<(Cout * Cin + 255) / 256, 256, 0, tg_stream(stream)>>>(w, w4, wp, Cout, Cin);
+  TG_LAUNCH((poolconv_weights_kernel), (Cout * Cin + 255) / 256, 256, tg_stream(stream), (w, w4, wp, Cout, Cin), "poolconv_weights_kernel;");
   return tg_launch_status();
 }
 
@@ -3391,7 +3492,8 @@ int tg_conv2d_wgrad(const float* x, const float* gy, float* gw, float* gbias, fl
   const int64_t E = (int64_t)Cout * Cin * ks * ks;
   float* bias_part = gbias ? workspace + (size_t)p.S * E : nullptr;
   const int blocks = (int)((E + 63) / 64) + (gbias ? (Cout + 63) / 64 : 0);
-  wgrad_reduce_kernel<<<blocks, 256, 0, st>>>(workspace, gw, E, p.S, bias_part, gbias, Cout, accumulate);
+  TG_LAUNCH((wgrad_reduce_kernel), blocks, 256, st, (workspace, gw, E, p.S, bias_part, gbias, Cout, accumulate),
+            "wgrad_reduce_kernel; bias=%d", gbias != nullptr);
   return tg_launch_status();
 }
 
@@ -3447,7 +3549,8 @@ int tg_conv1x1_multi_wgrad(const float* x, const float* gy0, const float* gy1, c
   hipStream_t st = tg_stream(stream);
   if (int rc = launch_conv1x1_wgrad_segs(x, three_segs(gy0, gy1, gy2, c0, c1, c2), workspace, nullptr, s, p.S, st)) return rc;
   const int64_t E = (int64_t)C * Cin;
-  wgrad_reduce_kernel<<<(int)((E + 63) / 64), 256, 0, st>>>(workspace, gw, E, p.S, nullptr, nullptr, C, accumulate);
+  TG_LAUNCH((wgrad_reduce_kernel), (int)((E + 63) / 64), 256, st, (workspace, gw, E, p.S, nullptr, nullptr, C, accumulate),
+            "wgrad_reduce_kernel; bias=0");
   return tg_launch_status();
 }
 
@@ -3471,7 +3574,7 @@ int tg_conv2d_wgrad_reduce_batch(const tg_host_i64* items, int n_items, void* st
         r->pad = 0;
         return (r->E + 63) / 64 + (r->gbias ? (Cout + 63) / 64 : 0);
       },
-      [st](const ReduceBatch& rb, unsigned blocks) { wgrad_reduce_batch_kernel<<<blocks, 256, 0, st>>>(rb); });
+      [st](const ReduceBatch& rb, unsigned blocks) { TG_LAUNCH((wgrad_reduce_batch_kernel), blocks, 256, st, (rb), "wgrad_reduce_batch_kernel; items=%d", rb.n); });
 }
 
 // ---- stage 1 of many 1x1 weight gradients in one launch (conv1x1_wgrad_grouped_kernel)
@@ -3516,7 +3619,83 @@ int tg_conv1x1_wgrad_partials_batch(const tg_host_i64* items, int n_items, void*
         w->Cin = Cin; w->Cout = Cout; w->HW = HW; w->S = p.S;
         return (int64_t)p.S * ((Cout + 16 * mt - 1) / (16 * mt)) * ((Cin + 16 * nt - 1) / (16 * nt));
       },
-      [st](const Wgrad1x1Batch& tb, unsigned blocks) { conv1x1_wgrad_grouped_kernel<<<blocks, 256, 0, st>>>(tb); });
+      [st](const Wgrad1x1Batch& tb, unsigned blocks) { TG_LAUNCH((conv1x1_wgrad_grouped_kernel), blocks, 256, st, (tb), "conv1x1_wgrad_grouped_kernel; items=%d", tb.n); });
+}
+
+// ---- which kernels would a call launch?  (host only, see the header)  Sets this thread's probe and makes the REAL call: the
+// entry point above, with addresses that are never dereferenced -- pointer k is (k + 1) << 32, four bytes further when bit k of
+// `unaligned` is set.  Every launch site then records instead of launching (TG_LAUNCH), and the switches read the probe.
+const char* tg_conv_dispatch(int op, int B, int Cin, int Cout, int H, int W, int ks, int c1, int c2, int unaligned, int has_bias,
+                             int has_residual, int wino, int dma, int prio) {
+  static thread_local TgProbe probe;
+  probe.out.clear();
+  probe.wino = wino; probe.dma = dma; probe.prio = prio;
+  int k = 0;
+  auto addr = [&]() { const int i = k++; return (uintptr_t)(i + 1) << 32 | ((unaligned >> i & 1) ? 4u : 0u); };
+  auto ptr = [&]() { return reinterpret_cast<float*>(addr()); };
+  auto opt = [&](int have) { float* p = ptr(); return have ? p : nullptr; };        // (a nullable pointer keeps its bit)
+  const size_t big = ~(size_t)0;                                                   // workspace bytes: always enough
+  const int c0 = Cout, acc = 0;
+  tg_probe = &probe;
+  int rc = TG_EINVAL;
+  switch (op) {
+    case TG_OP_CONV2D_FWD: { auto x = ptr(), w = ptr(), b = opt(has_bias), r = opt(has_residual);
+      rc = tg_conv2d_fwd(x, w, b, r, ptr(), B, Cin, Cout, H, W, ks, nullptr); break; }
+    case TG_OP_CONV2D_FWD_UP2RES: { auto x = ptr(), w = ptr(), b = opt(has_bias), r = ptr();
+      rc = tg_conv2d_fwd_up2res(x, w, b, r, ptr(), B, Cin, Cout, H, W, nullptr); break; }
+    case TG_OP_CONV2D_DGRAD: { auto gy = ptr(), w = ptr();
+      rc = tg_conv2d_dgrad(gy, w, ptr(), B, Cin, Cout, H, W, ks, nullptr); break; }
+    case TG_OP_CONV2D_WGRAD: { auto x = ptr(), gy = ptr(), gw = ptr(), gb = opt(has_bias);
+      rc = tg_conv2d_wgrad(x, gy, gw, gb, ptr(), big, B, Cin, Cout, H, W, ks, acc, nullptr); break; }
+    case TG_OP_CONV2D_WGRAD_PARTIALS: { auto x = ptr(), gy = ptr();
+      rc = tg_conv2d_wgrad_partials(x, gy, ptr(), big, B, Cin, Cout, H, W, ks, has_bias, nullptr); break; }
+    case TG_OP_CONV2D_WGRAD_REDUCE_BATCH: case TG_OP_S2_WGRAD_REDUCE_BATCH: {
+      const tg_host_i64 part = (tg_host_i64)addr(), gw = (tg_host_i64)addr(), gb = (tg_host_i64)addr();
+      const tg_host_i64 row[TG_WGRAD_ITEM_FIELDS] = {part, gw, has_bias ? gb : 0, B, Cin, Cout, H, W, ks, acc};   // (ks: the mode, for the stride-2 form)
+      rc = op == TG_OP_S2_WGRAD_REDUCE_BATCH ? tg_s2_wgrad_reduce_batch(row, 1, nullptr) : tg_conv2d_wgrad_reduce_batch(row, 1, nullptr);
+      break; }
+    case TG_OP_CONV1X1_WGRAD_PARTIALS_BATCH: {
+      const tg_host_i64 x = (tg_host_i64)addr(), g0 = (tg_host_i64)addr(), g1 = (tg_host_i64)addr(), g2 = (tg_host_i64)addr(), ws = (tg_host_i64)addr();
+      const tg_host_i64 row[TG_WGRAD1X1_ITEM_FIELDS] = {x, g0, c1 ? g1 : 0, c2 ? g2 : 0, ws, INT64_MAX, c0, c1, c2, B, Cin, H, W, ks, has_bias};
+      rc = tg_conv1x1_wgrad_partials_batch(row, 1, nullptr); break; }
+    case TG_OP_UPCONV3X3_WEIGHTS: { auto w = ptr(); rc = tg_upconv3x3_weights(w, ptr(), Cout, Cin, nullptr); break; }
+    case TG_OP_UPCONV3X3_WEIGHTS_T: { auto w = ptr(); rc = tg_upconv3x3_weights_t(w, ptr(), Cout, Cin, nullptr); break; }
+    case TG_OP_UPCONV3X3_WEIGHTS_PAIR: { auto w = ptr(), wp = ptr(); rc = tg_upconv3x3_weights_pair(w, wp, ptr(), Cout, Cin, nullptr); break; }
+    case TG_OP_UPCONV3X3_FWD: { auto a = ptr(), wp = ptr(), b = opt(has_bias), r = opt(has_residual);
+      rc = tg_upconv3x3_fwd(a, wp, b, r, ptr(), B, Cin, Cout, H, W, nullptr); break; }
+    case TG_OP_UPCONV3X3_DGRAD: { auto gy = ptr(), w4t = ptr();
+      rc = tg_upconv3x3_dgrad(gy, w4t, ptr(), B, Cin, Cout, H, W, nullptr); break; }
+    case TG_OP_UPCONV3X3_WGRAD: case TG_OP_POOLCONV3X3_WGRAD: { auto p0 = ptr(), p1 = ptr(), gw = ptr(), ws = ptr(), gb = opt(has_bias);
+      rc = op == TG_OP_UPCONV3X3_WGRAD ? tg_upconv3x3_wgrad(p0, p1, gw, ws, big, B, Cin, Cout, H, W, acc, gb, nullptr)
+                                       : tg_poolconv3x3_wgrad(p0, p1, gw, ws, big, B, Cin, Cout, H, W, acc, gb, nullptr);
+      break; }
+    case TG_OP_UPCONV3X3_WGRAD_PARTIALS: case TG_OP_POOLCONV3X3_WGRAD_PARTIALS: { auto p0 = ptr(), p1 = ptr();
+      rc = op == TG_OP_UPCONV3X3_WGRAD_PARTIALS ? tg_upconv3x3_wgrad_partials(p0, p1, ptr(), big, B, Cin, Cout, H, W, has_bias, nullptr)
+                                                : tg_poolconv3x3_wgrad_partials(p0, p1, ptr(), big, B, Cin, Cout, H, W, has_bias, nullptr);
+      break; }
+    case TG_OP_POOLCONV3X3_WEIGHTS: { auto w = ptr(), w4 = ptr(); rc = tg_poolconv3x3_weights(w, w4, ptr(), Cout, Cin, nullptr); break; }
+    case TG_OP_POOLCONV3X3_WEIGHTS_BATCH: {
+      const tg_host_i64 w = (tg_host_i64)addr(), w4 = (tg_host_i64)addr(), wp = (tg_host_i64)addr();
+      const tg_host_i64 row[TG_FORM_ITEM_FIELDS] = {w, w4, wp, Cout, Cin};
+      rc = tg_poolconv3x3_weights_batch(row, 1, nullptr); break; }
+    case TG_OP_POOLCONV3X3_FWD: { auto x = ptr(), w4 = ptr(), b = opt(has_bias), r = opt(has_residual);
+      rc = tg_poolconv3x3_fwd(x, w4, b, r, ptr(), B, Cin, Cout, H, W, nullptr); break; }
+    case TG_OP_POOLCONV3X3_DGRAD: { auto gy = ptr(), wp = ptr();
+      rc = tg_poolconv3x3_dgrad(gy, wp, ptr(), B, Cin, Cout, H, W, nullptr); break; }
+    case TG_OP_RGB_COMPOSE_FWD: { auto w1 = ptr(), b1 = ptr(), w3 = ptr(); rc = tg_rgb_compose_fwd(w1, b1, w3, ptr(), Cout, Cin, ks, nullptr); break; }
+    case TG_OP_RGB_COMPOSE_BWD: { auto gwc = ptr(), w1 = ptr(), b1 = ptr(), w3 = ptr(), gw1 = ptr(), gb1 = ptr();
+      rc = tg_rgb_compose_bwd(gwc, w1, b1, w3, gw1, gb1, ptr(), Cout, Cin, ks, acc, nullptr); break; }
+    case TG_OP_CONV1X1_MULTI_FWD: { auto x = ptr(), w = ptr(), y0 = ptr(), y1 = ptr();
+      rc = tg_conv1x1_multi_fwd(x, w, y0, y1, ptr(), c0, c1, c2, B, Cin, H, W, nullptr); break; }
+    case TG_OP_CONV1X1_MULTI_DGRAD: { auto g0 = ptr(), g1 = ptr(), g2 = ptr(), w = ptr();
+      rc = tg_conv1x1_multi_dgrad(g0, g1, g2, w, ptr(), c0, c1, c2, B, Cin, H, W, nullptr); break; }
+    case TG_OP_CONV1X1_MULTI_WGRAD: { auto x = ptr(), g0 = ptr(), g1 = ptr(), g2 = ptr(), gw = ptr();
+      rc = tg_conv1x1_multi_wgrad(x, g0, g1, g2, gw, ptr(), big, c0, c1, c2, B, Cin, H, W, acc, nullptr); break; }
+    default: break;
+  }
+  tg_probe = nullptr;
+  if (rc != TG_OK) probe.out += "rc=" + std::to_string(rc) + "\n";
+  return probe.out.c_str();
 }
 
 }  // extern "C"
