@@ -737,6 +737,24 @@ int tg_latent_step(float* z, const float* gz, float* m, float* v, int64_t* step,
  * which equals the reference's int(a * b / S) for every index in range.  Copy-exact.  A non-positive dimension: TG_EINVAL.   */
 int tg_mosaic_gather(const float* imgs, float* out, int rows, int cols, int C, int h, int w, int S, void* stream);
 
+/* ---------------------------------------------------------------- dataset building (tartangan_amd/image_folder_dataset.py, csrc/dataset.hip; tg_version 110)
+ * Pillow's two-pass separable resampler for 8-bit interleaved images (Resample.c, 8bpc) with host-supplied fixed-point taps: what
+ * Image.resize((OW, OH), LANCZOS) computes, bit for bit, for a batch of same-shaped images.
+ *   src (N, H, W, C), dst (N, OH, OW, C), C = 1 or 3 (otherwise TG_EUNSUPPORTED)
+ *   kx (OW, ksx) int32 taps scaled by 2^22, bx (OW, 2) = (first input column, tap count) per output column; ky (OH, ksy), by (OH, 2)
+ *   the same for rows.  kx null: no horizontal pass, W == OW required; ky null: no vertical pass, H == OH required; both null is
+ *   TG_EINVAL (the caller copies).  With both passes tmp is (N, H, OW, C): HORIZONTAL FIRST, the intermediate clipped to uint8.
+ * Per output sample: acc = 2^21 + sum_j pixel[first + j] * k[j] in 32 bits with unsigned wrap-around, out = clip((int32)acc >> 22,
+ * 0, 255).  No atomics; integer sums are order-free.  The byte pointers may sit at any address, the int32 tables at any multiple
+ * of 4; all indexing is 64-bit.
+ * The bounds decide what is read, so they are copied to the host and checked before anything is launched (the call synchronises
+ * the stream and does not replay from a graph): first < 0, count < 0, count > ks or first + count past the input is TG_EINVAL, as
+ * are a null src / dst / bounds / missing tmp and a non-positive size; nothing is written then.  TG_EUNSUPPORTED: the input span
+ * of 64 neighbouring output columns exceeds 64 KiB (about 21 000 RGB pixels): resize such an image on the host.              */
+int tg_resample_u8(const uint8_t* src, uint8_t* dst, uint8_t* tmp /*nullable*/, const int32_t* kx /*nullable*/,
+                   const int32_t* bx /*nullable*/, const int32_t* ky /*nullable*/, const int32_t* by /*nullable*/, int N, int H,
+                   int W, int C, int OH, int OW, int ksx, int ksy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

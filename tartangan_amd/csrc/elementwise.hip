@@ -435,7 +435,7 @@ int tg_ema(float* t, const float* p, float lr, int64_t n, void* stream) {
   return tg_launch_status();
 }
 
-int tg_version(void) { return 109; }
+int tg_version(void) { return 110; }
 const char* tg_arch(void) { return "gfx950"; }
 
 }  // extern "C"

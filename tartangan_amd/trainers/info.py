@@ -139,6 +139,11 @@ class InfoTrainer(CNNTrainer):
 
     # ------------------------------------------------------------------ flags
     @classmethod
+    def get_component_classes(cls, args):
+        from .components import InfoImageSamplerComponent
+        return super().get_component_classes(args) + [InfoImageSamplerComponent]      # info.py:107-110
+
+    @classmethod
     def add_args_to_parser(cls, p):
         super().add_args_to_parser(p)
         p.add_argument('--info-cat-dims', type=int, default=10)
@@ -147,4 +152,8 @@ class InfoTrainer(CNNTrainer):
 
 
 def main():
-    raise SystemExit('The CLI/epoch loop stays with tartangan; see INTEGRATION.md for the drop-in.')
+    InfoTrainer.create_from_cli().train()
+
+
+if __name__ == '__main__':
+    main()

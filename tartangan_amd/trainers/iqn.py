@@ -35,3 +35,11 @@ class IQNTrainer(CNNTrainer):
     def _g_loss(self, fake, ones):
         _, g_loss = self.d(fake, targets=ones)
         return g_loss
+
+
+def main():
+    IQNTrainer.create_from_cli().train()
+
+
+if __name__ == '__main__':
+    main()

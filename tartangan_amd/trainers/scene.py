@@ -60,4 +60,8 @@ class SceneTrainer(CNNTrainer):
 
 
 def main():
-    raise SystemExit('The CLI/epoch loop stays with tartangan; see INTEGRATION.md for the drop-in.')
+    SceneTrainer.create_from_cli().train()
+
+
+if __name__ == '__main__':
+    main()

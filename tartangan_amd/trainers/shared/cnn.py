@@ -52,4 +52,8 @@ class CNNTrainer(_cnn.CNNTrainer):
 
 
 def main():
-    raise SystemExit('The CLI/epoch loop stays with tartangan; see INTEGRATION.md for the drop-in.')
+    CNNTrainer.create_from_cli().train()
+
+
+if __name__ == '__main__':
+    main()

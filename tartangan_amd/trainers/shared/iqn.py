@@ -32,4 +32,8 @@ class IQNTrainer(CNNTrainer):
 
 
 def main():
-    raise SystemExit('The CLI/epoch loop stays with tartangan; see INTEGRATION.md for the drop-in.')
+    IQNTrainer.create_from_cli().train()
+
+
+if __name__ == '__main__':
+    main()

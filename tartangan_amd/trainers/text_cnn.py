@@ -69,6 +69,25 @@ class TextCNNTrainer(Trainer):
         from .components.text_sampler import TextSamplerComponent
         self.attach(ModelCheckpointComponent(), TextSamplerComponent())
 
+    @classmethod
+    def get_component_classes(cls, args):
+        """The pair ``setup_components`` attaches (text_cnn.py:128-131), for the command line."""
+        from .components.model_checkpoint import ModelCheckpointComponent
+        from .components.text_sampler import TextSamplerComponent
+        super().get_component_classes(args)          # (refuses a metrics collector)
+        return [ModelCheckpointComponent, TextSamplerComponent]
+
+    @classmethod
+    def check_data_path(cls, path):
+        import os
+        return None if os.path.isfile(path) else f'{path} is not a pickled frame of documents'
+
+    def batches(self):
+        """The reference's ``DataLoader(dataset, batch_size, shuffle=True, drop_last=True)`` itself (trainer.py:84-86)."""
+        from torch.utils.data import DataLoader
+        loader = DataLoader(self.dataset, batch_size=self.args.batch_size, shuffle=True, drop_last=True)
+        return loader, len(loader)
+
     # ------------------------------------------------------------------ the step
     def enable_graphs(self):
         raise NotImplementedError('TextCNNTrainer does not replay from HIP graphs (integer draws and the pretraining switch are host-side)')
@@ -160,4 +179,8 @@ class TextCNNTrainer(Trainer):
 
 
 def main():
-    raise SystemExit('The CLI/epoch loop stays with tartangan; see INTEGRATION.md for the drop-in.')
+    TextCNNTrainer.create_from_cli().train()
+
+
+if __name__ == '__main__':
+    main()

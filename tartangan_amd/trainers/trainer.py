@@ -1,19 +1,29 @@
-"""Hot-path half of the reference's ``Trainer`` (trainers/trainer.py).
+"""The reference's ``Trainer`` (trainers/trainer.py) on the HIP engine.
 
-In scope: the latent / batch assembly helpers
-``sample_z / sample_g / make_adversarial_batch / make_generator_batch``
-(trainer.py:153-176) and the hyper-parameter flags of the step
-(trainer.py:268-313).  The epoch loop, datasets, callbacks and filesystem
-handling of the reference stay with the reference: a tartangan ``Trainer`` calls
-``train_batch(images)`` once per DataLoader batch (trainer.py:96) and that call
-is the drop-in boundary.
+The hot-path half: the latent / batch assembly helpers ``sample_z / sample_g / make_adversarial_batch /
+make_generator_batch`` (trainer.py:153-176) and the hyper-parameter flags of the step (trainer.py:268-313).  A tartangan
+``Trainer`` can still call ``train_batch(images)`` once per DataLoader batch (trainer.py:96): that call is the drop-in boundary.
+
+The driving half: ``prepare_dataset`` (a folder of images resized on the device, or a uint8 archive), ``train`` -- the reference's
+epoch loop (trainer.py:80-115), event for event -- and ``create_from_cli``, the two-stage command line (trainer.py:236-267) with
+the reference's flags.  A trainer constructed directly takes no part in any of it: no run id is generated, nothing is written.
 """
 import argparse
+import hashlib
+import os
+import random
+import string
+import sys
+import time
+from collections import defaultdict
+from datetime import datetime
 
 import numpy as np
 import torch
 
 from .utils import set_device_from_args
+
+NONE_WORDS = (None, 'None', 'none')
 
 
 def write_codes(z, cat_dims, cats):
@@ -277,6 +287,160 @@ class Trainer:
     def train_batch(self, imgs):
         raise NotImplementedError
 
+    # ------------------------------------------------------------------ the epoch loop (trainer.py:53-123)
+    def prepare_dataset(self):
+        """A directory: every image file under it squashed to the model size (``ImageFolderDataset``), from the dataset cache when
+        ``--dataset-cache`` names one that exists.  Anything else: a uint8 archive (.npz / .npy), cropped at random to the model size."""
+        from ..image_bytes_dataset import ImageBytesDataset
+        from ..image_folder_dataset import ImageFolderDataset
+        size, path = self.g.max_size, self.args.data_path
+        if os.path.isdir(path):
+            cache = self.dataset_cache_path(size) if getattr(self.args, 'dataset_cache', None) else None
+            return ImageFolderDataset(path, size, device=self.device, cache_path=cache)
+        return ImageBytesDataset.from_path(path, crop_size=size, device=self.device)
+
+    def dataset_cache_path(self, size):
+        root = getattr(getattr(self, 'dataset', None), 'root', None) or os.path.expanduser(self.args.data_path)
+        return self.args.dataset_cache.format(root=hashlib.md5(root.encode('utf-8')).hexdigest(), size=size)
+
+    def batches(self):
+        """One epoch of batches -> (iterable, how many).  The order is a ``DataLoader(shuffle=True, drop_last=True)``'s."""
+        dp = self.data_parallel
+        rank, world = (dp.rank, dp.world) if dp is not None else (0, 1)
+        return (self.dataset.loader(self.args.batch_size, rank=rank, world=world),
+                len(self.dataset) // (self.args.batch_size * world))
+
+    def invoke(self, event, *args):
+        """Every component's ``on_<event>`` hook, in the order the components were attached (components/container.py:14-18)."""
+        for component in self.components:
+            getattr(component, f'on_{event}')(*args)
+
+    def train(self):
+        self.build_models()
+        if getattr(self.args, 'graphs', False):
+            self.enable_graphs()
+        print(f'Preparing dataset from {self.args.data_path}')
+        self.dataset = self.prepare_dataset()
+        logs = defaultdict(list)
+        try:
+            self.invoke('train_begin', self.steps, logs)
+            while self.epoch <= self.args.epochs:
+                print(f'Starting epoch {self.epoch}')
+                self.invoke('epoch_begin', self.steps, self.epoch, logs)
+                progress = self._progress(*self.batches())
+                for images in progress:
+                    self.invoke('batch_begin', self.steps, logs)
+                    step = self.steps
+                    training_metrics = self.train_batch(images)
+                    self.steps = step          # train_batch counts its own calls; the loop's count moves after batch_end, as the reference's
+                    for name, value in training_metrics.items():
+                        logs[name].append(value)
+                    self.invoke('batch_end', self.steps, logs)
+                    progress.set_postfix(refresh=False, **{k: round(v, 4) for k, v in training_metrics.items()})
+                    self.steps += 1
+                self.invoke('epoch_end', self.steps, self.epoch, logs)
+                if self.epoch == 1 and getattr(self.args, 'cache_dataset', False) and hasattr(self.dataset, 'save_cache'):
+                    self.dataset.save_cache(self.dataset_cache_path(self.g.max_size))
+                self.epoch += 1
+        except KeyboardInterrupt:
+            pass          # graceful interrupt
+        self.invoke('train_end', self.steps, logs)
+        return logs
+
+    def _progress(self, iterable, total):
+        """tqdm when it can be imported and ``--log-progress-newlines`` is off, plain lines otherwise; ``--quiet-logs`` reports every
+        ``--log-iters`` batches only."""
+        args = self.args
+        quiet, every = getattr(args, 'quiet_logs', False), getattr(args, 'log_iters', 1000)
+        if not getattr(args, 'log_progress_newlines', False):
+            try:
+                import tqdm
+            except ImportError:
+                pass
+            else:
+                return tqdm.tqdm(iterable, total=total, **(dict(mininterval=0, maxinterval=np.inf, miniters=every) if quiet else {}))
+        return LineProgress(iterable, total, every if quiet else None)
+
+    # ------------------------------------------------------------------ the command line (trainer.py:218-313)
+    @classmethod
+    def get_component_classes(cls, args):
+        from .components import FIDComponent, ImageSamplerComponent, ModelCheckpointComponent
+        collector = getattr(args, 'metrics_collector', None)
+        if collector not in NONE_WORDS:
+            raise SystemExit(f'--metrics-collector {collector}: the katib / kubeflow / tensorboard writers are not part of '
+                             f'tartangan_amd (DESIGN.md section 10); run without the flag')
+        classes = [ImageSamplerComponent, ModelCheckpointComponent]
+        if getattr(args, 'fid', False):
+            classes.append(FIDComponent)
+        return classes
+
+    @classmethod
+    def _parser(cls, component_classes=()):
+        # 'resolve': the samplers bring --gen-freq themselves; the loop's own definition is the same flag
+        p = argparse.ArgumentParser(description='TartanGAN trainer', fromfile_prefix_chars='@', conflict_handler='resolve')
+        cls.add_args_to_parser(p)
+        cls.add_loop_args_to_parser(p)
+        for component_class in component_classes:
+            component_class.add_args_to_parser(p)
+        return p
+
+    @classmethod
+    def check_data_path(cls, path):
+        """-> why ``path`` cannot be trained from, or None.  Asked before the run directory is made."""
+        from ..image_folder_dataset import IMG_EXTENSIONS
+        if os.path.isdir(path):
+            for _, _, files in os.walk(path):
+                if any(os.path.splitext(name)[1] in IMG_EXTENSIONS for name in files):
+                    return None
+            return f'no image files ({", ".join(IMG_EXTENSIONS)}) under {path}'
+        if not os.path.isfile(path):
+            return f'{path} does not exist'
+        if os.path.splitext(path)[1] not in ('.npz', '.npy'):
+            return f'{path} is neither a folder of images nor a uint8 archive (.npz / .npy)'
+        return None
+
+    @classmethod
+    def create_from_cli(cls, argv=None):
+        """Instantiate from the command line (``argv`` default: ``sys.argv[1:]``).  Two stages, as in the reference: the trainer's
+        own flags decide which components run, then those add theirs.  The run id, the run directory and its ``config.args`` (the
+        arguments, one per line: ``@config.args`` repeats the run) are made here."""
+        argv = list(sys.argv[1:] if argv is None else argv)
+        base_args = cls._parser().parse_known_args(argv)[0]
+        component_classes = cls.get_component_classes(base_args)
+        parser = cls._parser(component_classes)
+        args = parser.parse_args(argv)
+        problem = cls.check_data_path(args.data_path)
+        if problem:
+            parser.error(problem)
+        set_device_from_args(args)
+        print(f'Using device "{args.device}"')
+        if args.run_id is None:
+            args.run_id = generate_run_id()
+        trainer = cls(args)
+        os.makedirs(trainer.output_root, exist_ok=True)
+        save_cli_arguments(f'{trainer.output_root}/config.args', argv)
+        return trainer.attach(*[component_class(args) for component_class in component_classes])
+
+    @classmethod
+    def add_loop_args_to_parser(cls, p):
+        """The reference's flags of the loop (trainer.py:271-313) that ``add_args_to_parser`` -- the flags of the step, which
+        ``default_args`` parses with nothing on the line -- leaves out, and ``--graphs``."""
+        p.add_argument('data_path', help='A folder of images, or a uint8 image archive (.npz / .npy)')
+        p.add_argument('--gen-freq', type=int, default=200, help='Output samples every N batches')
+        p.add_argument('--epochs', type=int, default=10000)
+        p.add_argument('--output', default='output', help='Root of output locations. A path segment unique to the run will be appended.')
+        p.add_argument('--dataset-cache', default='cache/{root}_{size}.pkl', help='Location of the dataset cache of an image folder')
+        p.add_argument('--cache-dataset', action='store_true', help='Write the dataset cache after the first epoch')
+        p.add_argument('--quiet-logs', action='store_true', help='Reduce log output')
+        p.add_argument('--log-iters', type=int, default=1000, help='Progress logging frequency when --quiet-logs are enabled')
+        p.add_argument('--log-progress-newlines', action='store_true', help='Log progress updates one per line')
+        p.add_argument('--metrics-collector', default=None, help='Not available here (katib, kubeflow, tensorboard in the reference)')
+        p.add_argument('--run-id', type=lambda v: None if v in NONE_WORDS else str(v), default=None,
+                       help='Explicitly set a run id. Otherwise, one will be generated automatically.')
+        p.add_argument('--fid', action='store_true', help='Calculate FID test metric')
+        # not in the reference
+        p.add_argument('--graphs', action='store_true', help='Replay the step from captured HIP graphs (enable_graphs())')
+
     # ------------------------------------------------------------------ flags of the step
     @classmethod
     def add_args_to_parser(cls, p):
@@ -304,3 +468,40 @@ class Trainer:
         for k, v in overrides.items():
             setattr(args, k, v)
         return args
+
+
+def generate_run_id(suffix_len=6):
+    """``<date>_<time>_<six random letters>`` (trainer.py:205-208)."""
+    now = datetime.now().strftime('%Y-%m-%d_%H-%M-%S')
+    return f"{now}_{''.join(random.sample(string.ascii_letters, suffix_len))}"
+
+
+def save_cli_arguments(filename, argv, fromfile_prefix='@'):
+    """The arguments, one per line, in a form ``@filename`` reads back; a lone ``@file`` argument is copied out (utils/cli.py:6-23)."""
+    lines = list(argv)
+    if lines and lines[0].startswith(fromfile_prefix):
+        with open(lines[0][1:]) as f:
+            lines = [line.strip() for line in f.readlines()] + lines[1:]
+    with open(filename, 'w') as f:
+        f.write('\n'.join(lines))
+
+
+class LineProgress:
+    """Progress as plain lines: every ``every`` batches, or at most one line a second."""
+
+    def __init__(self, iterable, total, every=None):
+        self.iterable, self.total, self.every = iterable, total, every
+        self.postfix = {}
+
+    def set_postfix(self, refresh=False, **values):
+        self.postfix = values
+
+    def __iter__(self):
+        start = last = time.monotonic()
+        for i, item in enumerate(self.iterable, 1):
+            yield item
+            now = time.monotonic()
+            if (i % self.every == 0) if self.every else (now - last >= 1.0 or i == self.total):
+                last = now
+                rate = i / max(now - start, 1e-9)
+                print(f'{i}/{self.total} [{rate:.2f}it/s] ' + ', '.join(f'{k}={v}' for k, v in self.postfix.items()), flush=True)
