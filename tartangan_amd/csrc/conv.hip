@@ -1527,14 +1527,14 @@ static int launch_conv1x1_wgrad_segs(const float* x, ChanSegs gy, float* part, f
   const int64_t groups = (int64_t)s.B * (HW / 16);
   const int mt = conv1x1_wgrad_mt(s.Cout), nt = conv1x1_wgrad_nt(s.Cin);
   dim3 grid(S, (s.Cout + 16 * mt - 1) / (16 * mt), (s.Cin + 16 * nt - 1) / (16 * nt));
-#define TG_WG1_ARGS (x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S)
-#define TG_WG1_FMT " bias=%d gysegs=%d", bias_part != nullptr, gy.start[1] < s.Cout ? 3 : 1
-  if (mt == 1 && nt == 1) TG_LAUNCH((conv1x1_wgrad_stream_kernel<1, 1>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<1, 1>;" TG_WG1_FMT);
-  else if (mt == 1) TG_LAUNCH((conv1x1_wgrad_stream_kernel<1, 2>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<1, 2>;" TG_WG1_FMT);
-  else if (nt == 1) TG_LAUNCH((conv1x1_wgrad_stream_kernel<2, 1>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<2, 1>;" TG_WG1_FMT);
-  else TG_LAUNCH((conv1x1_wgrad_stream_kernel<2, 2>), grid, 256, st, TG_WG1_ARGS, "conv1x1_wgrad_stream_kernel<2, 2>;" TG_WG1_FMT);
-#undef TG_WG1_ARGS
-#undef TG_WG1_FMT
+#define TG_WG1(MT, NT)                                                                                                       \
+  TG_LAUNCH((conv1x1_wgrad_stream_kernel<MT, NT>), grid, 256, st, (x, gy, part, bias_part, s.Cin, s.Cout, HW, groups, S),    \
+            "conv1x1_wgrad_stream_kernel<%d, %d>; bias=%d gysegs=%d", MT, NT, bias_part != nullptr, gy.start[1] < s.Cout ? 3 : 1)
+  if (mt == 1 && nt == 1) TG_WG1(1, 1);
+  else if (mt == 1) TG_WG1(1, 2);
+  else if (nt == 1) TG_WG1(2, 1);
+  else TG_WG1(2, 2);
+#undef TG_WG1
   return tg_launch_status();
 }
 static int launch_conv1x1_wgrad_stream(const float* x, const float* gy, float* part, float* bias_part, Shape s, int S, hipStream_t st) {
@@ -2734,37 +2734,62 @@ static inline GeoId pick_geo(int H, int W) {
   if (H == 16 && W == 16) return GEO_16;
   return GEO_X;
 }
-static inline int geo_tiles(GeoId g, int B, int H, int W) {
-  switch (g) {
-    case GEO_4: return num_tiles<G4>(B, H, W);
-    case GEO_8: return num_tiles<G8>(B, H, W);
-    case GEO_16: return num_tiles<G16>(B, H, W);
-    default: return num_tiles<GX>(B, H, W);
-  }
+// The one place where that run-time choice becomes a type: f(G{}) for the geometry among Gs that `g` names (generic lambdas and
+// decltype at the call sites), `other` when it names none of them.  Gs: the 256-pixel geometries a kernel family is instantiated
+// for; f -- and with it the kernels -- is instantiated in the order they are listed, which is the order of the kernels in the library.
+template <class G>
+constexpr GeoId geo_id = std::is_same_v<G, G4> ? GEO_4 : std::is_same_v<G, G8> ? GEO_8 : std::is_same_v<G, G16> ? GEO_16 : GEO_X;
+template <class... Gs, class R, class F>
+static inline R with_geo(GeoId g, R other, F&& f) {
+  (void)(... || (g == geo_id<Gs> && (other = f(Gs{}), true)));
+  return other;
 }
+// the 64-pixel K-split geometry of the same planes (8 x 32 tiles have none)
+template <class G> struct KSplit;
+template <> struct KSplit<G4> { using type = G4k; };
+template <> struct KSplit<G8> { using type = G8k; };
+template <> struct KSplit<G16> { using type = G16k; };
+
+static inline int geo_tiles(GeoId g, int B, int H, int W) {
+  return with_geo<G4, G8, G16, GX>(g, 0, [&](auto geo) { return num_tiles<decltype(geo)>(B, H, W); });
+}
+// the LDS-DMA staged 3x3 kernels (direct, Winograd, pooled Winograd) take planes of whole tiles: 16 x 16, or whole 8 x 32 tiles
+static inline bool whole_tiles(GeoId g, int H, int W) { return g == GEO_16 || (g == GEO_X && H % 8 == 0 && W % 32 == 0); }
 
 // 16-byte row loads need W % 4 == 0 and a 16-byte aligned base
 static inline int plane_vec_ok(const void* p, int W) { return (W % 4 == 0) && tg_aligned16(p); }
 // stride-2 family: low-resolution planes of 8x8 (4 images per tile), 16x16 and larger; workgroups needed to pay off
 static inline bool s2_geo(GeoId g) { return g == GEO_8 || g == GEO_16 || g == GEO_X; }
 static inline int64_t s2_min_wgs(GeoId g) { return g == GEO_8 ? 128 : 256; }
-// (ARGS in parentheses; after them the flags part of the probe's record, see TG_LAUNCH)
-#define TG_S2_DISPATCH(g, KERNEL, ARGS, ...)                                                                          \
-  do {                                                                                                                \
-    if ((g) == GEO_8) TG_LAUNCH((KERNEL<G8>), grid, CT_THREADS, st, ARGS, #KERNEL "<G8>;" __VA_ARGS__);               \
-    else if ((g) == GEO_16) TG_LAUNCH((KERNEL<G16>), grid, CT_THREADS, st, ARGS, #KERNEL "<G16>;" __VA_ARGS__);       \
-    else TG_LAUNCH((KERNEL<GX>), grid, CT_THREADS, st, ARGS, #KERNEL "<GX>;" __VA_ARGS__);                            \
-  } while (0)
 
-// records of the four stride-2 forward-type families: LDS-DMA staged (`t` tiles in scope) / register staged
-#define TG_S2D_REC " swz=%d prio=%d bias=%d res=%d", t % 8 == 0, s.prio, bias != nullptr, residual != nullptr
-#define TG_S2R_REC " vx=%d vw=%d bias=%d res=%d", vx, vw, bias != nullptr, residual != nullptr
+// ---- The three switches, read once from the environment: TG_CONV_DMA=0 sends every launch to the register-staged kernels
+// (the tests use it to reach them at small shapes), TG_DMA_PRIO=1 see conv_dma_kernel; TG_CONV_WINO=0 disables the Winograd
+// forms (wino.h), 2 takes every eligible shape (tests), 1 (default) only the launches that fill the chip: 64-tile workgroups on
+// 8x8 / 4x4 planes give too few workgroups at the step's batch.
+// (A probe -- tg_conv_dispatch -- may carry its own value of each switch, for its call only.)
+static bool dma_enabled() {
+  static const bool v = [] { const char* e = getenv("TG_CONV_DMA"); return !e || atoi(e) != 0; }();
+  return (tg_probe && tg_probe->dma >= 0) ? tg_probe->dma != 0 : v;
+}
+static int dma_prio() {
+  static const int v = [] { const char* e = getenv("TG_DMA_PRIO"); return e ? atoi(e) : 0; }();
+  return (tg_probe && tg_probe->prio >= 0) ? tg_probe->prio : v;
+}
+static int wino_mode() {
+  static const int v = [] { const char* e = getenv("TG_CONV_WINO"); return e ? atoi(e) : 1; }();
+  return (tg_probe && tg_probe->wino >= 0) ? tg_probe->wino : v;
+}
 
-// stride-2 transpose form: 8x8 planes that give fewer than 256 four-image tiles run as single-image K-split tiles
-static bool s2_dma_ok(const void* x, const void* w, const Shape& s, int hi_channels);
-static int dma_prio();
+// stride-2 kernels: whole 16-byte chunks (the callers checked plane / filter alignment), channel counts that keep filter rows
+// 16-byte aligned (x 16 or x 4 floats per channel pair: always), 32-bit buffer offsets; hi_channels > 0: the input is the
+// high-resolution tensor (4x the plane)
+static bool s2_dma_ok(const void* x, const void* w, const Shape& s, int hi_channels) {
+  if (!dma_enabled()) return false;
+  const int64_t plane = (int64_t)s.H * s.W * (hi_channels ? 4 : 1);
+  if ((int64_t)s.B * s.Cin * plane * 4 >= (1ll << 31) || (int64_t)s.Cin * s.Cout * 64 * 4 >= (1ll << 31)) return false;
+  return s.W % 4 == 0 || hi_channels;        // low-resolution rows of whole chunks (high-resolution rows: 2 W, the caller's vx)
+}
 
-static int wino_mode();
 // AvgPool2d(2) o conv3x3 in its 9-frequency form (conv_poolwino_dma_kernel, wino.h) -> true when it took the launch
 static bool try_launch_poolwino(const float* x, const float* w4, const float* bias, const float* residual, float* y, const Shape& s,
                                 int vx, hipStream_t st) {
@@ -2774,94 +2799,74 @@ static bool try_launch_poolwino(const float* x, const float* w4, const float* bi
       (int64_t)s.B * s.Cin * s.H * s.W * 16 >= (1ll << 31))
     return false;
   const int Hh = 2 * s.H, Wh = 2 * s.W;
+  const GeoId g = pick_geo(Hh, Wh);
+  if (!whole_tiles(g, Hh, Wh)) return false;
   const int cob = (s.Cout + 31) / 32;
   const int64_t min_wgs = (mode == 2) ? 1 : 256;
-  if (Hh % 8 == 0 && Wh % 32 == 0) {
-    const int tiles = num_tiles<GX>(s.B, Hh, Wh);
+  return with_geo<GX, G16>(g, false, [&](auto geo) {
+    using G = decltype(geo);
+    const int tiles = num_tiles<G>(s.B, Hh, Wh), flags = (tiles % 8 == 0) ? 1 : 0;
     if ((int64_t)tiles * cob < min_wgs) return false;
-    TG_LAUNCH((conv_poolwino_dma_kernel<GX, 2>), dim3(tiles, cob), CT_THREADS, st, (x, w4, bias, residual, y, s, (tiles % 8 == 0) ? 1 : 0),
-              "conv_poolwino_dma_kernel<GX, 2>; flags=%d bias=%d res=%d", (tiles % 8 == 0) ? 1 : 0, bias != nullptr, residual != nullptr);
+    TG_LAUNCH((conv_poolwino_dma_kernel<G, 2>), dim3(tiles, cob), CT_THREADS, st, (x, w4, bias, residual, y, s, flags),
+              "conv_poolwino_dma_kernel<%s, 2>; flags=%d bias=%d res=%d", geo_name<G>(), flags, bias != nullptr, residual != nullptr);
     return true;
-  }
-  if (Hh == 16 && Wh == 16) {
-    const int tiles = num_tiles<G16>(s.B, Hh, Wh);
-    if ((int64_t)tiles * cob < min_wgs) return false;
-    TG_LAUNCH((conv_poolwino_dma_kernel<G16, 2>), dim3(tiles, cob), CT_THREADS, st, (x, w4, bias, residual, y, s, (tiles % 8 == 0) ? 1 : 0),
-              "conv_poolwino_dma_kernel<G16, 2>; flags=%d bias=%d res=%d", (tiles % 8 == 0) ? 1 : 0, bias != nullptr, residual != nullptr);
-    return true;
-  }
-  return false;
+  });
 }
 
-static void launch_upT(GeoId g, const float* x, const float* w4, const float* bias, const float* residual, float* y, Shape s,
-                       int vx, int vw, hipStream_t st) {
-  if (try_launch_poolwino(x, w4, bias, residual, y, s, vx, st)) return;
-  const int cot = (s.Cout + 15) / 16;
-  if (vx && vw && s2_dma_ok(x, w4, s, s.Cin)) {            // LDS-DMA staged forms
-    s.prio = dma_prio();
-    if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
-      const int t = num_tiles<G8k>(s.B, s.H, s.W);
-      TG_LAUNCH((conv_upT_dma_kernel<G8k, true>), dim3(t, cot), CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
-                "conv_upT_dma_kernel<G8k, true>;" TG_S2D_REC);
-      return;
-    }
-    const int t = geo_tiles(g, s.B, s.H, s.W);
-    dim3 grid(t, cot);
-    if (g == GEO_8) TG_LAUNCH((conv_upT_dma_kernel<G8, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
-                              "conv_upT_dma_kernel<G8, false>;" TG_S2D_REC);
-    else if (g == GEO_16) TG_LAUNCH((conv_upT_dma_kernel<G16, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
-                                    "conv_upT_dma_kernel<G16, false>;" TG_S2D_REC);
-    else TG_LAUNCH((conv_upT_dma_kernel<GX, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, t % 8 == 0),
-                   "conv_upT_dma_kernel<GX, false>;" TG_S2D_REC);
-    return;
-  }
-  if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
-    TG_LAUNCH((conv_upT_kernel<G8k, true>), dim3(num_tiles<G8k>(s.B, s.H, s.W), cot), CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
-              "conv_upT_kernel<G8k, true>;" TG_S2R_REC);
-    return;
-  }
-  dim3 grid(geo_tiles(g, s.B, s.H, s.W), cot);
-  if (g == GEO_8) TG_LAUNCH((conv_upT_kernel<G8, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
-                            "conv_upT_kernel<G8, false>;" TG_S2R_REC);
-  else if (g == GEO_16) TG_LAUNCH((conv_upT_kernel<G16, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
-                                  "conv_upT_kernel<G16, false>;" TG_S2R_REC);
-  else TG_LAUNCH((conv_upT_kernel<GX, false>), grid, CT_THREADS, st, (x, w4, bias, residual, y, s, vx, vw),
-                 "conv_upT_kernel<GX, false>;" TG_S2R_REC);
-}
+// ---- The two stride-2 forward-type families: an LDS-DMA staged kernel and its register-staged twin, under the names the records
+// give them
+struct S2UpT {        // AvgPool2d(2) o conv3x3 forward, and the dgrad of conv3x3 o nearest_up2x
+  template <class G, bool WK> static constexpr auto dma = conv_upT_dma_kernel<G, WK>;
+  template <class G, bool WK> static constexpr auto reg = conv_upT_kernel<G, WK>;
+  static constexpr const char *dma_name = "conv_upT_dma_kernel", *reg_name = "conv_upT_kernel";
+};
+struct S2UpFwd {      // conv3x3 o nearest_up2x forward (all four phases in one kernel), and the dgrad of AvgPool2d(2) o conv3x3
+  template <class G, bool WK> static constexpr auto dma = conv_upfwd_dma_kernel<G, WK>;
+  template <class G, bool WK> static constexpr auto reg = conv_upfwd_kernel<G, WK>;
+  static constexpr const char *dma_name = "conv_upfwd_dma_kernel", *reg_name = "conv_upfwd_kernel";
+};
 
-static void launch_upfwd(GeoId g, const float* x, const float* wp, const float* bias, const float* residual, float* y, Shape s,
-                         int vx, int vw, hipStream_t st) {
+// family F's kernel of one staging, for the planes `g` names (the callers checked s2_geo(g))
+template <class F, bool DMA>
+static int launch_s2_staged(GeoId g, const float* x, const float* w, const float* bias, const float* residual, float* y, const Shape& s,
+                            int vx, int vw, hipStream_t st) {
   const int cot = (s.Cout + 15) / 16;
-  if (vx && vw && s2_dma_ok(x, wp, s, 0)) {
+  auto launch = [&](auto geo) {
+    using G = decltype(geo);
+    constexpr bool WK = (G::NPIX == 64);
+    const int t = num_tiles<G>(s.B, s.H, s.W);
+    if constexpr (DMA)
+      TG_LAUNCH((F::template dma<G, WK>), dim3(t, cot), CT_THREADS, st, (x, w, bias, residual, y, s, t % 8 == 0),
+                "%s<%s, %s>; swz=%d prio=%d bias=%d res=%d", F::dma_name, geo_name<G>(), tf(WK), t % 8 == 0, s.prio, bias != nullptr,
+                residual != nullptr);
+    else
+      TG_LAUNCH((F::template reg<G, WK>), dim3(t, cot), CT_THREADS, st, (x, w, bias, residual, y, s, vx, vw),
+                "%s<%s, %s>; vx=%d vw=%d bias=%d res=%d", F::reg_name, geo_name<G>(), tf(WK), vx, vw, bias != nullptr, residual != nullptr);
+    return tg_launch_status();
+  };
+  // 8x8 planes that give fewer than 256 four-image tiles run as single-image K-split tiles
+  if (g == GEO_8 && (int64_t)num_tiles<G8>(s.B, s.H, s.W) * cot < 256) return launch(G8k{});
+  return with_geo<G8, G16, GX>(g, TG_EUNSUPPORTED, launch);
+}
+// one launch of family F: LDS-DMA staged when the operands allow it (hi_channels: see s2_dma_ok)
+template <class F>
+static int launch_s2(GeoId g, const float* x, const float* w, const float* bias, const float* residual, float* y, Shape s, int vx, int vw,
+                     int hi_channels, hipStream_t st) {
+  if (vx && vw && s2_dma_ok(x, w, s, hi_channels)) {
     s.prio = dma_prio();
-    if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
-      const int t = num_tiles<G8k>(s.B, s.H, s.W);
-      TG_LAUNCH((conv_upfwd_dma_kernel<G8k, true>), dim3(t, cot), CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
-                "conv_upfwd_dma_kernel<G8k, true>;" TG_S2D_REC);
-      return;
-    }
-    const int t = geo_tiles(g, s.B, s.H, s.W);
-    dim3 grid(t, cot);
-    if (g == GEO_8) TG_LAUNCH((conv_upfwd_dma_kernel<G8, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
-                              "conv_upfwd_dma_kernel<G8, false>;" TG_S2D_REC);
-    else if (g == GEO_16) TG_LAUNCH((conv_upfwd_dma_kernel<G16, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
-                                    "conv_upfwd_dma_kernel<G16, false>;" TG_S2D_REC);
-    else TG_LAUNCH((conv_upfwd_dma_kernel<GX, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, t % 8 == 0),
-                   "conv_upfwd_dma_kernel<GX, false>;" TG_S2D_REC);
-    return;
+    return launch_s2_staged<F, true>(g, x, w, bias, residual, y, s, vx, vw, st);
   }
-  if (g == GEO_8 && (int64_t)geo_tiles(g, s.B, s.H, s.W) * cot < 256) {
-    TG_LAUNCH((conv_upfwd_kernel<G8k, true>), dim3(num_tiles<G8k>(s.B, s.H, s.W), cot), CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
-              "conv_upfwd_kernel<G8k, true>;" TG_S2R_REC);
-    return;
-  }
-  dim3 grid(geo_tiles(g, s.B, s.H, s.W), cot);
-  if (g == GEO_8) TG_LAUNCH((conv_upfwd_kernel<G8, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
-                            "conv_upfwd_kernel<G8, false>;" TG_S2R_REC);
-  else if (g == GEO_16) TG_LAUNCH((conv_upfwd_kernel<G16, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
-                                  "conv_upfwd_kernel<G16, false>;" TG_S2R_REC);
-  else TG_LAUNCH((conv_upfwd_kernel<GX, false>), grid, CT_THREADS, st, (x, wp, bias, residual, y, s, vx, vw),
-                 "conv_upfwd_kernel<GX, false>;" TG_S2R_REC);
+  return launch_s2_staged<F, false>(g, x, w, bias, residual, y, s, vx, vw, st);
+}
+// (the transpose form reads the high-resolution tensor, and its pooled Winograd form comes first)
+static int launch_upT(GeoId g, const float* x, const float* w4, const float* bias, const float* residual, float* y, const Shape& s, int vx,
+                      int vw, hipStream_t st) {
+  if (try_launch_poolwino(x, w4, bias, residual, y, s, vx, st)) return tg_launch_status();
+  return launch_s2<S2UpT>(g, x, w4, bias, residual, y, s, vx, vw, s.Cin, st);
+}
+static int launch_upfwd(GeoId g, const float* x, const float* wp, const float* bias, const float* residual, float* y, const Shape& s, int vx,
+                        int vw, hipStream_t st) {
+  return launch_s2<S2UpFwd>(g, x, wp, bias, residual, y, s, vx, vw, 0, st);
 }
 
 template <class G, int KS, bool DGRAD>
@@ -2903,28 +2908,7 @@ int launch_fwd_geo(const float* x, const float* w, const float* bias, const floa
   return tg_launch_status();
 }
 
-// ---- LDS-DMA kernel dispatch.  Two switches, read once from the environment: TG_CONV_DMA=0 sends every launch to the
-// register-staged kernels (the tests use it to reach them at small shapes), TG_DMA_PRIO=1 see conv_dma_kernel.
-// (A probe -- tg_conv_dispatch -- may carry its own value of each switch, for its call only.)
-static bool dma_enabled() {
-  static const bool v = [] { const char* e = getenv("TG_CONV_DMA"); return !e || atoi(e) != 0; }();
-  return (tg_probe && tg_probe->dma >= 0) ? tg_probe->dma != 0 : v;
-}
-static int dma_prio() {
-  static const int v = [] { const char* e = getenv("TG_DMA_PRIO"); return e ? atoi(e) : 0; }();
-  return (tg_probe && tg_probe->prio >= 0) ? tg_probe->prio : v;
-}
-
-// stride-2 kernels: whole 16-byte chunks (the callers checked plane / filter alignment), channel counts that keep filter rows
-// 16-byte aligned (x 16 or x 4 floats per channel pair: always), 32-bit buffer offsets; hi_channels > 0: the input is the
-// high-resolution tensor (4x the plane)
-static bool s2_dma_ok(const void* x, const void* w, const Shape& s, int hi_channels) {
-  if (!dma_enabled()) return false;
-  const int64_t plane = (int64_t)s.H * s.W * (hi_channels ? 4 : 1);
-  if ((int64_t)s.B * s.Cin * plane * 4 >= (1ll << 31) || (int64_t)s.Cin * s.Cout * 64 * 4 >= (1ll << 31)) return false;
-  return s.W % 4 == 0 || hi_channels;        // low-resolution rows of whole chunks (high-resolution rows: 2 W, the caller's vx)
-}
-
+// ---- LDS-DMA kernel dispatch
 // (G, DGRAD, the operands, `s` and `swz` -- bit 0: swizzled tile order, bit 5: TG_DMA_PRIO -- of the enclosing function)
 #define TG_DMA(MF, MT, CK_, GRID)                                                                                                   \
   TG_LAUNCH((conv_dma_kernel<G, MF, MT, CK_, DGRAD>), GRID, CT_THREADS, st, (x, w, bias, residual, y, s, swz),                        \
@@ -2972,29 +2956,23 @@ static bool try_launch_dma(const float* x, const float* w, const float* bias, co
   if ((int64_t)s.B * s.Cin * s.H * s.W * 4 >= (1ll << 31) || (int64_t)s.Cin * s.Cout * 36 >= (1ll << 31)) return false;
   // channel chunk: 4 keeps more workgroups resident (17 KB of LDS) and wins on the short-K layers; 8 halves the barriers
   const bool ck4 = s.Cin <= 16;
-  bool took = false;
-  if (s.H % 8 == 0 && s.W % 32 == 0) {
-    took = ck4 ? launch_dma_geo<GX, 4, DGRAD>(x, w, bias, residual, y, s, st) : launch_dma_geo<GX, 8, DGRAD>(x, w, bias, residual, y, s, st);
-  } else if (s.H == 16 && s.W == 16) {
-    took = ck4 ? launch_dma_geo<G16, 4, DGRAD>(x, w, bias, residual, y, s, st) : launch_dma_geo<G16, 8, DGRAD>(x, w, bias, residual, y, s, st);
-  }
+  const GeoId g = pick_geo(s.H, s.W);
+  bool took = whole_tiles(g, s.H, s.W) && with_geo<GX, G16>(g, false, [&](auto geo) {
+    using G = decltype(geo);
+    return ck4 ? launch_dma_geo<G, 4, DGRAD>(x, w, bias, residual, y, s, st) : launch_dma_geo<G, 8, DGRAD>(x, w, bias, residual, y, s, st);
+  });
   if (!took && s.Cin >= 16) {
     // small planes with long K: 64-pixel tiles, the four waves split each 16-channel chunk (one workgroup per CU is the
     // normal case here, so the chunk DMA under the MFMAs is the only overlap there is)
-    if (s.H == 8 && s.W == 8) took = launch_dma_ksplit<G8k, DGRAD>(x, w, bias, residual, y, s, st);
-    else if (s.H == 4 && s.W == 4) took = launch_dma_ksplit<G4k, DGRAD>(x, w, bias, residual, y, s, st);
-    else if (s.H == 16 && s.W == 16) took = launch_dma_ksplit<G16k, DGRAD>(x, w, bias, residual, y, s, st);
+    took = with_geo<G8, G4, G16>(g, false, [&](auto geo) {
+      return launch_dma_ksplit<typename KSplit<decltype(geo)>::type, DGRAD>(x, w, bias, residual, y, s, st);
+    });
   }
   if (took) *rc = tg_launch_status();
   return took;
 }
 
-// ---- Winograd F(2x2, 3x3) dispatch (wino.h).  TG_CONV_WINO=0 disables it, 2 takes every eligible shape (tests), 1 (default)
-// only the launches that fill the chip: 64-tile workgroups on 8x8 / 4x4 planes give too few workgroups at the step's batch.
-static int wino_mode() {
-  static const int v = [] { const char* e = getenv("TG_CONV_WINO"); return e ? atoi(e) : 1; }();
-  return (tg_probe && tg_probe->wino >= 0) ? tg_probe->wino : v;
-}
+// ---- Winograd F(2x2, 3x3) dispatch (wino.h)
 // (G, DGRAD, the operands, `s` and `flags` -- bit 0: swizzled tile order -- of the enclosing function)
 #define TG_WINO(NB, CK_, KSPLIT, GRID)                                                                                           \
   TG_LAUNCH((conv_wino_dma_kernel<G, NB, DGRAD, CK_, KSPLIT>), GRID, CT_THREADS, st, (x, w, bias, residual, y, s, flags),           \
@@ -3046,14 +3024,19 @@ static bool try_launch_wino(const float* x, const float* w, const float* bias, c
     return false;
   const int64_t min_wgs = (mode == 2) ? 1 : 256;
   // (64-tile workgroups on 8x8 / 4x4 planes give too few workgroups at the step's batch: mode 2 only)
+  const GeoId g = pick_geo(s.H, s.W);
   int r = -1;
-  if (s.H % 8 == 0 && s.W % 32 == 0) r = launch_wino_geo<GX, DGRAD>(x, w, bias, residual, y, s, st, min_wgs);
-  // (16x16 planes at batch 64 -- exactly one workgroup per CU -- measured neutral to slightly slower inside the step: from two per CU)
-  else if (s.H == 16 && s.W == 16) r = launch_wino_geo<G16, DGRAD>(x, w, bias, residual, y, s, st, mode == 2 ? 1 : 512);
-  // 8x8 / 4x4 planes, K-split form: measured SLOWER than the direct K-split kernels (128 -> 128 @8^2, batch 64 / 128: 20.5 / 39.1 us
-  // against 17.1 / 28.8; the step 9.29 against 9.21 ms) -- a workgroup transforms a whole filter chunk for 16 tiles; mode 2 only
-  else if (mode == 2 && s.H == 8 && s.W == 8) r = launch_wino_ksplit<G8k, DGRAD>(x, w, bias, residual, y, s, st, min_wgs);
-  else if (mode == 2 && s.H == 4 && s.W == 4) r = launch_wino_ksplit<G4k, DGRAD>(x, w, bias, residual, y, s, st, min_wgs);
+  if (whole_tiles(g, s.H, s.W)) {
+    // (16x16 planes at batch 64 -- exactly one workgroup per CU -- measured neutral to slightly slower inside the step: from two per CU)
+    const int64_t geo_wgs = (g == GEO_16 && mode != 2) ? 512 : min_wgs;
+    r = with_geo<GX, G16>(g, -1, [&](auto geo) { return launch_wino_geo<decltype(geo), DGRAD>(x, w, bias, residual, y, s, st, geo_wgs); });
+  } else if (mode == 2) {
+    // 8x8 / 4x4 planes, K-split form: measured SLOWER than the direct K-split kernels (128 -> 128 @8^2, batch 64 / 128: 20.5 / 39.1 us
+    // against 17.1 / 28.8; the step 9.29 against 9.21 ms) -- a workgroup transforms a whole filter chunk for 16 tiles; mode 2 only
+    r = with_geo<G8, G4>(g, -1, [&](auto geo) {
+      return launch_wino_ksplit<typename KSplit<decltype(geo)>::type, DGRAD>(x, w, bias, residual, y, s, st, min_wgs);
+    });
+  }
   if (r < 0) return false;
   *rc = r;
   return true;
@@ -3082,12 +3065,13 @@ int launch_fwd(const float* x, const float* w, const float* bias, const float* r
   const GeoId g = pick_geo(s.H, s.W);
   const int64_t wgs256 = (int64_t)geo_tiles(g, s.B, s.H, s.W) * ((s.Cout + 63) / 64);
   const bool ksplit = (g != GEO_X) && wgs256 < 128 && s.Cin >= 16;
-  switch (g) {
-    case GEO_4: return ksplit ? launch_fwd_geo<G4k, KS, DGRAD>(x, w, bias, residual, y, s, st) : launch_fwd_geo<G4, KS, DGRAD>(x, w, bias, residual, y, s, st);
-    case GEO_8: return ksplit ? launch_fwd_geo<G8k, KS, DGRAD>(x, w, bias, residual, y, s, st) : launch_fwd_geo<G8, KS, DGRAD>(x, w, bias, residual, y, s, st);
-    case GEO_16: return ksplit ? launch_fwd_geo<G16k, KS, DGRAD>(x, w, bias, residual, y, s, st) : launch_fwd_geo<G16, KS, DGRAD>(x, w, bias, residual, y, s, st);
-    default: return launch_fwd_geo<GX, KS, DGRAD>(x, w, bias, residual, y, s, st);
-  }
+  return with_geo<G4, G8, G16, GX>(g, TG_EUNSUPPORTED, [&](auto geo) {
+    using G = decltype(geo);
+    if constexpr (!std::is_same_v<G, GX>) {
+      if (ksplit) return launch_fwd_geo<typename KSplit<G>::type, KS, DGRAD>(x, w, bias, residual, y, s, st);
+    }
+    return launch_fwd_geo<G, KS, DGRAD>(x, w, bias, residual, y, s, st);
+  });
 }
 
 struct WgPlan {
@@ -3159,12 +3143,9 @@ int launch_wgrad_geo(const float* x, const float* gy, float* part, float* bias_p
 
 template <int KS>
 int launch_wgrad(const float* x, const float* gy, float* part, float* bias_part, Shape s, const WgPlan& p, hipStream_t st) {
-  switch (pick_geo(s.H, s.W)) {
-    case GEO_4: return launch_wgrad_geo<G4, KS>(x, gy, part, bias_part, s, p, st);
-    case GEO_8: return launch_wgrad_geo<G8, KS>(x, gy, part, bias_part, s, p, st);
-    case GEO_16: return launch_wgrad_geo<G16, KS>(x, gy, part, bias_part, s, p, st);
-    default: return launch_wgrad_geo<GX, KS>(x, gy, part, bias_part, s, p, st);
-  }
+  return with_geo<G4, G8, G16, GX>(pick_geo(s.H, s.W), TG_EUNSUPPORTED, [&](auto geo) {
+    return launch_wgrad_geo<decltype(geo), KS>(x, gy, part, bias_part, s, p, st);
+  });
 }
 
 static inline int check_shape(int B, int Cin, int Cout, int H, int W, int ks) {
@@ -3178,6 +3159,17 @@ static inline int check_shape(int B, int Cin, int Cout, int H, int W, int ks) {
   if ((int64_t)H * W >= (1 << 24) || cmax * 9 >= (1 << 24) || ni * cmax * H * W >= (1ll << 30)) return TG_EUNSUPPORTED;
   return TG_OK;
 }
+
+// one row of a TG_WGRAD_ITEM_FIELDS table (tartangan_amd.h)
+struct WgradRow {
+  const float* part;
+  float *gw, *gbias;
+  int B, Cin, Cout, H, W, ks, accumulate;      // (ks: the mode, for the stride-2 form)
+  static WgradRow from(const tg_host_i64* it) {
+    return {reinterpret_cast<const float*>(it[0]), reinterpret_cast<float*>(it[1]), reinterpret_cast<float*>(it[2]),
+            (int)it[3], (int)it[4], (int)it[5], (int)it[6], (int)it[7], (int)it[8], (int)it[9]};
+  }
+};
 
 }  // namespace
 
@@ -3209,31 +3201,30 @@ int tg_upconv3x3_weights(const float* w, float* wp, int Cout, int Cin, void* str
   return tg_launch_status();
 }
 
+// conv3x3 o nearest_up2x as one 2x2-tap launch per output phase (scalar stores: any y), `wp` the four phase filters in a row
+static int launch_up_phases(const float* x, const float* wp, const float* bias, const float* residual, float* y, Shape s, hipStream_t st) {
+  s.os = 2;
+  for (int ph = 0; ph < 4; ++ph) {
+    s.oy = s.py = ph >> 1;
+    s.ox = s.px = ph & 1;
+    if (int rc = launch_fwd<2, false>(x, wp + (size_t)ph * s.Cout * s.Cin * 4, bias, residual, y, s, st)) return rc;
+  }
+  return TG_OK;
+}
+
 int tg_upconv3x3_fwd(const float* a, const float* wp, const float* bias, const float* residual, float* y, int B, int Cin, int Cout,
                      int H, int W, void* stream) {
   TG_CHECK_PTR(a); TG_CHECK_PTR(wp); TG_CHECK_PTR(y);
   if (int rc = check_shape(B, Cin, Cout, 2 * H, 2 * W, 3)) return rc;      // the output plane is the large one
   hipStream_t st = tg_stream(stream);
-  {
-    // one kernel for all four phases when the low-resolution plane gives enough 256-pixel tiles
-    Shape s{B, Cin, Cout, H, W};
-    const GeoId g = pick_geo(H, W);
-    const int cot = (Cout + 15) / 16;
-    const bool aligned8 = (((uintptr_t)y & 7) == 0) && (!residual || ((uintptr_t)residual & 7) == 0);
-    if (s2_geo(g) && aligned8 && (int64_t)geo_tiles(g, B, H, W) * cot >= s2_min_wgs(g)) {
-      const int vx = plane_vec_ok(a, W), vw = tg_aligned16(wp);
-      launch_upfwd(g, a, wp, bias, residual, y, s, vx, vw, st);
-      return tg_launch_status();
-    }
-  }
-  for (int ph = 0; ph < 4; ++ph) {
-    Shape s{B, Cin, Cout, H, W};
-    s.oy = s.py = ph >> 1;
-    s.ox = s.px = ph & 1;
-    s.os = 2;
-    if (int rc = launch_fwd<2, false>(a, wp + (size_t)ph * Cout * Cin * 4, bias, residual, y, s, st)) return rc;
-  }
-  return TG_OK;
+  const Shape s{B, Cin, Cout, H, W};
+  // one kernel for all four phases when the low-resolution plane gives enough 256-pixel tiles
+  const GeoId g = pick_geo(H, W);
+  const int cot = (Cout + 15) / 16;
+  const bool aligned8 = (((uintptr_t)y & 7) == 0) && (!residual || ((uintptr_t)residual & 7) == 0);
+  if (s2_geo(g) && aligned8 && (int64_t)geo_tiles(g, B, H, W) * cot >= s2_min_wgs(g))
+    return launch_upfwd(g, a, wp, bias, residual, y, s, plane_vec_ok(a, W), tg_aligned16(wp), st);
+  return launch_up_phases(a, wp, bias, residual, y, s, st);
 }
 
 int tg_upconv3x3_weights_t(const float* w, float* w4t, int Cout, int Cin, void* stream) {
@@ -3259,10 +3250,7 @@ int tg_upconv3x3_dgrad(const float* gy, const float* w4t, float* ga, int B, int 
   if (!tg_upconv3x3_dgrad_supported(B, Cin, Cout, H, W)) return TG_EUNSUPPORTED;
   // a convolution whose input channels are the forward's Cout (gy) and output channels its Cin (ga)
   Shape s{B, Cout, Cin, H, W};
-  const GeoId g = pick_geo(H, W);
-  const int vx = plane_vec_ok(gy, 2 * W), vw = tg_aligned16(w4t);
-  launch_upT(g, gy, w4t, nullptr, nullptr, ga, s, vx, vw, tg_stream(stream));
-  return tg_launch_status();
+  return launch_upT(pick_geo(H, W), gy, w4t, nullptr, nullptr, ga, s, plane_vec_ok(gy, 2 * W), tg_aligned16(w4t), tg_stream(stream));
 }
 
 static inline int s2_splits(int tiles, int lo_tiles, int hi_chunks) {
@@ -3273,21 +3261,19 @@ static inline int s2_splits(int tiles, int lo_tiles, int hi_chunks) {
   if (S > tiles) S = tiles;
   return S;
 }
-// workspace: S partials of T, then S partials of the bias gradient (over the wider of the two channel counts)
-static size_t s2_workspace(int B, int Clo, int Chi, int H, int W) {
-  const GeoId g = pick_geo(H, W);
-  const int S = s2_splits(geo_tiles(g, B, H, W), (Clo + 15) / 16, (Chi + S2_CKW - 1) / S2_CKW);
-  return ((size_t)S * Clo * Chi * 16 + (size_t)S * (Clo > Chi ? Clo : Chi)) * sizeof(float);
-}
 struct S2Plan { int S, tiles, lo_tiles, hi_chunks; };
 static S2Plan s2_plan(int B, int Clo, int Chi, int H, int W) {
-  const GeoId g = pick_geo(H, W);
   S2Plan p;
-  p.tiles = geo_tiles(g, B, H, W);
+  p.tiles = geo_tiles(pick_geo(H, W), B, H, W);
   p.lo_tiles = (Clo + 15) / 16;
   p.hi_chunks = (Chi + S2_CKW - 1) / S2_CKW;
   p.S = s2_splits(p.tiles, p.lo_tiles, p.hi_chunks);
   return p;
+}
+// workspace: S partials of T, then S partials of the bias gradient (over the wider of the two channel counts)
+static size_t s2_workspace(int B, int Clo, int Chi, int H, int W) {
+  const int S = s2_plan(B, Clo, Chi, H, W).S;
+  return ((size_t)S * Clo * Chi * 16 + (size_t)S * (Clo > Chi ? Clo : Chi)) * sizeof(float);
 }
 // stage 1: per-workgroup partials of T (and of the bias gradient, want_bias) into ws
 static int s2_wgrad_stage1(const float* hi, const float* lo, float* ws, size_t ws_bytes, int B, int Clo, int Chi, int H, int W, int mode,
@@ -3303,11 +3289,19 @@ static int s2_wgrad_stage1(const float* hi, const float* lo, float* ws, size_t w
   const int vh = plane_vec_ok(hi, 2 * W), vl = plane_vec_ok(lo, W);
   if (vh && vl && dma_enabled() && (int64_t)B * (Chi > Clo ? Chi : Clo) * H * W * 16 < (1ll << 31)) {
     s.prio = dma_prio();
-    TG_S2_DISPATCH(g, conv_wgrad_s2_dma_kernel, (hi, lo, ws, s, tiles, S, bias_part, mode), " prio=%d bias=%d mode=%d", s.prio, bias_part != nullptr, mode);
-  } else {
-    TG_S2_DISPATCH(g, conv_wgrad_s2_kernel, (hi, lo, ws, s, tiles, S, vh, vl, bias_part, mode), " vh=%d vl=%d bias=%d mode=%d", vh, vl, bias_part != nullptr, mode);
+    return with_geo<G8, G16, GX>(g, TG_EUNSUPPORTED, [&](auto geo) {
+      using G = decltype(geo);
+      TG_LAUNCH((conv_wgrad_s2_dma_kernel<G>), grid, CT_THREADS, st, (hi, lo, ws, s, tiles, S, bias_part, mode),
+                "conv_wgrad_s2_dma_kernel<%s>; prio=%d bias=%d mode=%d", geo_name<G>(), s.prio, bias_part != nullptr, mode);
+      return tg_launch_status();
+    });
   }
-  return tg_launch_status();
+  return with_geo<G8, G16, GX>(g, TG_EUNSUPPORTED, [&](auto geo) {
+    using G = decltype(geo);
+    TG_LAUNCH((conv_wgrad_s2_kernel<G>), grid, CT_THREADS, st, (hi, lo, ws, s, tiles, S, vh, vl, bias_part, mode),
+              "conv_wgrad_s2_kernel<%s>; vh=%d vl=%d bias=%d mode=%d", geo_name<G>(), vh, vl, bias_part != nullptr, mode);
+    return tg_launch_status();
+  });
 }
 static FoldItem s2_fold_item(const float* ws, float* gw, float* gbias, int B, int Clo, int Chi, int H, int W, int Cout, int Cin, int mode,
                              int accumulate) {
@@ -3344,17 +3338,17 @@ int tg_s2_wgrad_reduce_batch(const tg_host_i64* items, int n_items, void* stream
   return tg_group_run<FoldBatch>(
       items, n_items, TG_WGRAD_ITEM_FIELDS,
       [](const tg_host_i64* it) {
-        const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], mode = (int)it[8];
-        if (it[0] == 0 || it[1] == 0 || (mode != 0 && mode != 1)) return (int)TG_EINVAL;
-        const int Clo = mode == 0 ? Cout : Cin, Chi = mode == 0 ? Cin : Cout;
-        if (!s2_geo(pick_geo(H, W)) || check_shape(B, Clo, Chi, 2 * H, 2 * W, 3) != TG_OK) return (int)TG_EUNSUPPORTED;
+        const WgradRow r = WgradRow::from(it);
+        if (!r.part || !r.gw || (r.ks != 0 && r.ks != 1)) return (int)TG_EINVAL;
+        const int Clo = r.ks == 0 ? r.Cout : r.Cin, Chi = r.ks == 0 ? r.Cin : r.Cout;
+        if (!s2_geo(pick_geo(r.H, r.W)) || check_shape(r.B, Clo, Chi, 2 * r.H, 2 * r.W, 3) != TG_OK) return (int)TG_EUNSUPPORTED;
         return (int)TG_OK;
       },
       [](const tg_host_i64* it, FoldItem* f) {
-        const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], mode = (int)it[8];
-        *f = s2_fold_item(reinterpret_cast<const float*>(it[0]), reinterpret_cast<float*>(it[1]), reinterpret_cast<float*>(it[2]), B,
-                          mode == 0 ? Cout : Cin, mode == 0 ? Cin : Cout, H, W, Cout, Cin, mode, (int)it[9]);
-        return (int64_t)f->pair_blocks + (f->gbias ? (Cout + 3) / 4 : 0);
+        const WgradRow r = WgradRow::from(it);
+        *f = s2_fold_item(r.part, r.gw, r.gbias, r.B, r.ks == 0 ? r.Cout : r.Cin, r.ks == 0 ? r.Cin : r.Cout, r.H, r.W, r.Cout, r.Cin, r.ks,
+                          r.accumulate);
+        return (int64_t)f->pair_blocks + (f->gbias ? (r.Cout + 3) / 4 : 0);
       },
       [st](const FoldBatch& fb, unsigned blocks) { TG_LAUNCH((s2wgrad_reduce_fold_batch_kernel), blocks, 256, st, (fb), "s2wgrad_reduce_fold_batch_kernel; items=%d", fb.n); });
 }
@@ -3427,10 +3421,7 @@ int tg_poolconv3x3_fwd(const float* x, const float* w4, const float* bias, const
   TG_CHECK_PTR(x); TG_CHECK_PTR(w4); TG_CHECK_PTR(y);
   if (!tg_poolconv3x3_supported(B, Cin, Cout, H, W)) return TG_EUNSUPPORTED;
   Shape s{B, Cin, Cout, H, W};
-  const GeoId g = pick_geo(H, W);
-  const int vx = plane_vec_ok(x, 2 * W), vw = tg_aligned16(w4);
-  launch_upT(g, x, w4, bias, residual, y, s, vx, vw, tg_stream(stream));
-  return tg_launch_status();
+  return launch_upT(pick_geo(H, W), x, w4, bias, residual, y, s, plane_vec_ok(x, 2 * W), tg_aligned16(w4), tg_stream(stream));
 }
 
 int tg_poolconv3x3_dgrad(const float* gy, const float* wp, float* gx, int B, int Cin, int Cout, int H, int W, void* stream) {
@@ -3438,22 +3429,11 @@ int tg_poolconv3x3_dgrad(const float* gy, const float* wp, float* gx, int B, int
   if (!tg_poolconv3x3_supported(B, Cin, Cout, H, W)) return TG_EUNSUPPORTED;
   hipStream_t st = tg_stream(stream);
   // the four-phase kernel with gy (Cout channels, H x W) as its low-resolution input and Cin output channels
-  if (((uintptr_t)gx & 7) == 0) {
-    Shape s{B, Cout, Cin, H, W};
-    const GeoId g = pick_geo(H, W);
-    const int vx = plane_vec_ok(gy, W), vw = tg_aligned16(wp);
-    launch_upfwd(g, gy, wp, nullptr, nullptr, gx, s, vx, vw, st);
-    return tg_launch_status();
-  }
+  const Shape s{B, Cout, Cin, H, W};
+  if (((uintptr_t)gx & 7) == 0)
+    return launch_upfwd(pick_geo(H, W), gy, wp, nullptr, nullptr, gx, s, plane_vec_ok(gy, W), tg_aligned16(wp), st);
   // gx off an 8-byte boundary (the kernel above stores float2 pairs): one launch per phase, as tg_upconv3x3_fwd does for such a y
-  for (int ph = 0; ph < 4; ++ph) {
-    Shape s{B, Cout, Cin, H, W};
-    s.oy = s.py = ph >> 1;
-    s.ox = s.px = ph & 1;
-    s.os = 2;
-    if (int rc = launch_fwd<2, false>(gy, wp + (size_t)ph * Cin * Cout * 4, nullptr, nullptr, gx, s, st)) return rc;
-  }
-  return TG_OK;
+  return launch_up_phases(gy, wp, nullptr, nullptr, gx, s, st);
 }
 
 int tg_conv2d_dgrad(const float* gy, const float* w, float* gx, int B, int Cin, int Cout, int H, int W, int ks, void* stream) {
@@ -3559,20 +3539,21 @@ int tg_conv2d_wgrad_reduce_batch(const tg_host_i64* items, int n_items, void* st
   return tg_group_run<ReduceBatch>(
       items, n_items, TG_WGRAD_ITEM_FIELDS,
       [](const tg_host_i64* it) {
-        if (it[0] == 0 || it[1] == 0) return (int)TG_EINVAL;
-        return (int)check_shape((int)it[3], (int)it[4], (int)it[5], (int)it[6], (int)it[7], (int)it[8]);
+        const WgradRow r = WgradRow::from(it);
+        if (!r.part || !r.gw) return (int)TG_EINVAL;
+        return (int)check_shape(r.B, r.Cin, r.Cout, r.H, r.W, r.ks);
       },
-      [](const tg_host_i64* it, ReduceItem* r) {
-        const int B = (int)it[3], Cin = (int)it[4], Cout = (int)it[5], H = (int)it[6], W = (int)it[7], ks = (int)it[8];
-        r->part = reinterpret_cast<const float*>(it[0]);
-        r->gw = reinterpret_cast<float*>(it[1]);
-        r->gbias = reinterpret_cast<float*>(it[2]);
-        r->E = (int64_t)Cout * Cin * ks * ks;
-        r->S = wgrad_plan(B, Cin, Cout, H, W, ks).S;
-        r->Cout = Cout;
-        r->accumulate = (int)it[9];
-        r->pad = 0;
-        return (r->E + 63) / 64 + (r->gbias ? (Cout + 63) / 64 : 0);
+      [](const tg_host_i64* it, ReduceItem* ri) {
+        const WgradRow r = WgradRow::from(it);
+        ri->part = r.part;
+        ri->gw = r.gw;
+        ri->gbias = r.gbias;
+        ri->E = (int64_t)r.Cout * r.Cin * r.ks * r.ks;
+        ri->S = wgrad_plan(r.B, r.Cin, r.Cout, r.H, r.W, r.ks).S;
+        ri->Cout = r.Cout;
+        ri->accumulate = r.accumulate;
+        ri->pad = 0;
+        return (ri->E + 63) / 64 + (ri->gbias ? (r.Cout + 63) / 64 : 0);
       },
       [st](const ReduceBatch& rb, unsigned blocks) { TG_LAUNCH((wgrad_reduce_batch_kernel), blocks, 256, st, (rb), "wgrad_reduce_batch_kernel; items=%d", rb.n); });
 }
